@@ -2,7 +2,7 @@
 """Headline benchmark: image-text pairs/sec of the CLIP retrieval hot path
 (ViT-B/16 + BERT-base dual-encoder forward + InfoNCE loss) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-also] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-also] [--no-cpu-baseline] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 launches itself: one process per GPU under `python -m torch.distributed.run` on 127.0.0.1 (RCCL);
 started under an external launcher (WORLD_SIZE set) it uses that one.
@@ -27,6 +27,9 @@ configuration this box can run under `also` (three warm-up + eight timed steps e
 durations, measured live on the launch stream in extra (untimed, single-stream) steps.  `cpu_baseline` times the
 imported reference (`kind: reference`, only where /root/reference exists) or the CPU oracle (`kind: port`, a torch-CPU
 restatement of the reference algorithm) on the host cores on a bounded sample of the same workload.
+
+`--dump-outputs DIR` writes what the headline workload's last timed step returned to its caller as DIR/<name>.npy (dump_outputs):
+the inputs and weights are seeded, so two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -201,6 +204,37 @@ def synth_batch(batch, seq, vocab, device, seed):
     return px, ids
 
 
+DUMP_BYTES = 60 << 20           # --dump-outputs: data bytes of all files together (the .npy headers stay well inside 64 MiB)
+DUMP_OUTPUT_SAMPLE = 1 << 21    # at most this many elements of one output (8 MiB): a fixed, seeded sample of a larger one
+DUMP_GRAD_SAMPLE = 1 << 15      # the same for one parameter's gradient (fewer, if the budget left after the outputs is short)
+
+
+def dump_outputs(dump_dir, outputs, grads):
+    """`--dump-outputs DIR`: write what the last timed step handed its caller as DIR/<name>.npy (float32, or float64 for
+    float64 tensors).  `outputs`: name -> tensor (the loss; forward()'s dict on the autograd path).  `grads`: parameter
+    name -> .grad, written as grad.<name>.npy.  A tensor larger than its cap is written flattened, as the elements at a fixed
+    set of flat indices (numpy seed 0, sorted) that depends only on its size and the cap: two runs sample the same elements."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+
+    def host(t, cap):
+        t = t.detach()
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1).index_select(0, torch.from_numpy(idx).to(t.device))
+        return t.double().cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+
+    arrays = [(k, host(v, DUMP_OUTPUT_SAMPLE)) for k, v in outputs.items()]
+    left = DUMP_BYTES - sum(a.nbytes for _, a in arrays)
+    cap = min(DUMP_GRAD_SAMPLE, max(0, left // 8 // max(1, len(grads))))
+    arrays += [("grad." + name, host(g, cap)) for name, g in grads.items()]
+    total = sum(a.nbytes for _, a in arrays)
+    assert total <= DUMP_BYTES, total
+    for name, a in arrays:
+        np.save(os.path.join(dump_dir, name + ".npy"), a)
+    return {"dir": dump_dir, "files": len(arrays), "bytes": total}
+
+
 def _cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -356,6 +390,8 @@ def relaunch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=%d" % args.gpus,
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + \
           [a for a in sys.argv[1:] if a != "--launcher"]
+    if args.dump_outputs:       # (the ranks run in ROOT: a relative DIR means the caller's directory; the last occurrence wins)
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", EZCLIP_BENCH_LAUNCHED="1")
     sys.exit(subprocess.run(cmd, env=env, cwd=ROOT).returncode)
 
@@ -570,9 +606,11 @@ def gflop_per_pair(wl):
     return (GFLOP_FWD_EXECUTED_PER_PAIR if cls_last else GFLOP_FWD_PER_PAIR), GFLOP_FWD_PER_PAIR
 
 
-def run_workload(name, c, steps, warmup, batch_override=0, text_dropout=0.0, profile=True, sustained_steps=0, sustained_seconds=20.0):
+def run_workload(name, c, steps, warmup, batch_override=0, text_dropout=0.0, profile=True, sustained_steps=0, sustained_seconds=20.0,
+                 dump_dir=None):
     """Build the model of workload `name`, run `warmup` untimed and exactly `steps` timed steps (barrier + synchronize on
-    both sides, MAX over ranks), then the roofline leg.  Returns the fields of the JSON line for this workload."""
+    both sides, MAX over ranks), then the roofline leg.  Returns the fields of the JSON line for this workload.  With `dump_dir`,
+    rank 0 writes what the last timed step returned to its caller there (dump_outputs), before anything else runs."""
     import torch.distributed as dist
     from easynlp_amd import lib as L
     from easynlp_amd import parallel as P
@@ -615,7 +653,7 @@ def run_workload(name, c, steps, warmup, batch_override=0, text_dropout=0.0, pro
         hf_all = [{"token_type_ids": torch.zeros_like(i_), "attention_mask": i_.ne(0).long()} for _, i_ in batches]
     counter = [0]
 
-    def step(which=None):
+    def step(which=None, keep=None):
         k = counter[0] % NBATCH if which is None else which
         counter[0] += 1
         px, ids = batches[k]
@@ -625,6 +663,8 @@ def run_workload(name, c, steps, warmup, batch_override=0, text_dropout=0.0, pro
                 for p in app.parameters():          # optimizer.zero_grad() of the Trainer loop (set_to_none, core/trainer.py:337)
                     p.grad = None
                 out = app(dict({"pixel_values": px, "input_ids": ids}, **hf_inputs))
+                if keep is not None:
+                    keep.update(out)
                 loss = app.compute_loss(out, [])["loss"]
                 loss.backward()
                 if world > 1:                       # what DDP's hooks do for the reference (not overlapped on this path)
@@ -632,6 +672,8 @@ def run_workload(name, c, steps, warmup, batch_override=0, text_dropout=0.0, pro
                 return loss.detach()
             with torch.no_grad():
                 out = app(dict({"pixel_values": px, "input_ids": ids}, **hf_inputs))
+                if keep is not None:
+                    keep.update(out)
                 return app.compute_loss(out, [])["loss"]
         if wl["backward"]:
             # the gradient all-reduce belongs to a training step (DDP in trainer.py:101-108): buckets of the flat gradient
@@ -665,11 +707,13 @@ def run_workload(name, c, steps, warmup, batch_override=0, text_dropout=0.0, pro
     # HIP events on the launch stream around the same K steps: a step ends with the main stream having joined the text
     # tower's side stream, so the closing event is behind all of the step's work.  Reported beside the host clock, never instead of it.
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    # --dump-outputs: the last timed step also leaves forward()'s dict (autograd path) in `last_out`
+    last_out = {} if dump_dir and rank == 0 else None
     t0 = time.perf_counter()
     ev0.record()
-    for _ in range(steps):
+    for i in range(steps):
         h0 = time.perf_counter()
-        loss = step()
+        loss = step(keep=last_out if i == steps - 1 else None)
         host_s += time.perf_counter() - h0                     # host time inside step(): the packed-text metadata poll makes the host
         rows_seen.append(app._engine.last_text_rows)          # wait for the device, so this tracks ms_per_step for packed workloads
     ev1.record()
@@ -688,6 +732,12 @@ def run_workload(name, c, steps, warmup, batch_override=0, text_dropout=0.0, pro
     else:
         fastest = elapsed
     step_ms = elapsed / steps * 1e3
+    dumped = None
+    if last_out is not None:
+        outputs = {k: v for k, v in last_out.items() if isinstance(v, torch.Tensor)}
+        outputs["loss"] = loss
+        dumped = dump_outputs(dump_dir, outputs, {n: p.grad for n, p in app.named_parameters() if p.grad is not None})
+        last_out.clear()
     loss_val = float(step(0).item())       # untimed: the loss on batch 0 (the batch the parity tests evaluate the oracle on)
     fence()
 
@@ -801,6 +851,8 @@ def run_workload(name, c, steps, warmup, batch_override=0, text_dropout=0.0, pro
     if buckets:
         out["grad_allreduce_buckets_mib"] = [round((e - s) * (2 if GRAD_BUCKET_DTYPE is not None else 4) / 2 ** 20, 1) for s, e in buckets]
         out["grad_allreduce_bucket_dtype"] = "bf16" if GRAD_BUCKET_DTYPE is not None else "f32"
+    if dumped:
+        out["dump_outputs"] = dumped
     if sustained:
         tf = sustained["value_second_half"] * gflop / 1e3                        # executed model TFLOP/s in the steady state
         sustained["model_mfma_frac_second_half"] = round(tf / PEAK_TFLOPS[wl["dtype"]], 4)
@@ -831,9 +883,15 @@ def main():
     ap.add_argument("--preflight", action="store_true",
                     help="N > 1 only: initialise RCCL, time one all-gather (4 MiB), one reduce-scatter and one 64 MiB all-reduce, print ONE "
                          "JSON line with the per-collective times and exit -- so that a first multi-GPU run that fails says WHERE")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the headline workload, write what its last timed step returned (the loss; forward()'s "
+                         "outputs on the autograd path; a fixed sample of every parameter gradient when it trains) as DIR/<name>.npy, "
+                         "float32 (float64 tensors as float64), at most 64 MiB in all; rank 0 only")
     ap.add_argument("--text-dropout", type=float, default=0.0,
                     help="BERT hidden / attention dropout probability and train() mode (reference default 0.1; BASELINE runs 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if int(os.environ.get("RANK", "0")) == 0 and not os.environ.get("EZCLIP_BENCH_LAUNCHED") and not os.environ.get("EZCLIP_NO_CANARY"):
         # is the box healthy?  A child process that imports only torch (libezclip_hip.so is not in it); a failure here is the
@@ -899,7 +957,8 @@ def main():
     c = Ctx()
     c.world, c.rank, c.device = world, rank, device
     sus = args.sustained_steps if world == 1 else 0
-    head = run_workload(args.workload, c, args.steps, args.warmup, args.batch, args.text_dropout, sustained_steps=sus)
+    head = run_workload(args.workload, c, args.steps, args.warmup, args.batch, args.text_dropout, sustained_steps=sus,
+                        dump_dir=args.dump_outputs)
     also = {}
     if not args.no_also:
         names = [n for n in args.also.split(",") if n] or (ALSO_N1 if world == 1 else ALSO_MULTI)
@@ -940,7 +999,7 @@ def main():
         }
         for k in ("loss", "host_ms_per_step", "ms_per_step_hip_events", "clock_mhz_timed_steps", "power_w_timed_steps", "batches_rotated", "pack_meta_in_timed_region", "ms_per_step_ranks", "text_tower_rows", "gflop_per_pair",
                   "model_tflops_per_gpu", "model_mfma_frac", "roofline", "time_share", "attention_tflops", "layernorm_gbps",
-                  "grad_allreduce_buckets_mib", "sustained"):
+                  "grad_allreduce_buckets_mib", "sustained", "dump_outputs"):
             if k in head:
                 out[k] = head[k]
         if also:

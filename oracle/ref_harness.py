@@ -13,6 +13,7 @@ uninstalled packages) does not run; (2) ``datasets.list_datasets`` stub
 """
 from __future__ import annotations
 
+import hashlib
 import json
 import os
 import sys
@@ -21,6 +22,33 @@ import types
 import torch
 
 REFERENCE_ROOT = os.environ.get("EASYNLP_REFERENCE", "/root/reference")
+
+
+FUZZ_DIGESTS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "reference_fuzz.json")
+FUZZ_CHUNK = 100
+
+
+def digest(obj) -> str:
+    """first 16 hex digits of the sha256 of ``repr(obj)``: values and container types (a tuple is not a list) of plain Python data"""
+    return hashlib.sha256(repr(obj).encode("utf-8")).hexdigest()[:16]
+
+
+def fuzz_digests(pairs) -> list:
+    """digest of every run of FUZZ_CHUNK consecutive [input, output] pairs of a fuzz corpus: what tools/make_golden_fuzz.py stores
+    for the reference's outputs in tests/golden/reference_fuzz.json"""
+    return [digest(pairs[i:i + FUZZ_CHUNK]) for i in range(0, len(pairs), FUZZ_CHUNK)]
+
+
+def check_fuzz(name, pairs, table=None) -> None:
+    """``pairs`` ([input, output] of this implementation) and ``table`` (its token -> id table) against the reference's digests"""
+    with open(FUZZ_DIGESTS, encoding="utf-8") as f:
+        want = json.load(f)[name]
+    if table is not None:
+        assert digest(sorted(table.items())) == want["table"], "token table differs from the reference's"
+    got = fuzz_digests(pairs)
+    assert len(got) == len(want["chunks"])
+    for i, (a, b) in enumerate(zip(got, want["chunks"])):
+        assert a == b, "one of these inputs is handled unlike the reference: %r" % [p[0] for p in pairs[i * FUZZ_CHUNK:(i + 1) * FUZZ_CHUNK]]
 
 
 def reference_available() -> bool:

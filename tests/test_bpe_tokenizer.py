@@ -1,18 +1,31 @@
 """The open_clip flavour's BPE tokenizer (easynlp_amd/appzoo/clip/bpe_tokenizer.py) against the reference's SimpleTokenizer /
 openclip_tokenize (modelzoo/models/clip/openclip_tokenizer.py, appzoo/clip/data.py:137-161): a fixture produced by the
-reference (tools/make_golden.py: run_bpe_case) and, when the checkout is present, a live fuzz comparison."""
+reference (tools/make_golden.py: run_bpe_case) and the digests of the reference's ids for a fuzz corpus (tools/make_golden_fuzz.py)."""
 import gzip
 import os
 import random
 
 import numpy as np
-import pytest
 import torch
 
 from easynlp_amd.appzoo.clip.bpe_tokenizer import SimpleTokenizer, byte_symbols, openclip_tokenize
 from oracle import ref_harness as R
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "openclip_bpe_corpus.npz")
+
+
+def fuzz_texts():
+    """the seeded fuzz corpus: words with BPE / regex / html edge cases, and random character soup"""
+    rnd = random.Random(3)
+    words = ["photo", "photograph", "cat", "dogs", "the", "red", "running", "it's", "they've", "I'M", "café", "中文", "猫图", "2023",
+             "100%", "&amp;", "&lt;b&gt;", "<start_of_text>", "<END_OF_TEXT>", "\U0001F600", "a_b-c", "...", "½", "x" * 30, "\t", "\n", "  "]
+    texts = []
+    for _ in range(3000):
+        t = " ".join(rnd.choice(words) for _ in range(rnd.randint(0, 12)))
+        if rnd.random() < 0.3:
+            t = "".join(rnd.choice("abcdefghij klmno'.,!?-_#中文é\t") for _ in range(rnd.randint(0, 30)))
+        texts.append(t)
+    return texts
 
 
 def _tok(tmp_path):
@@ -47,18 +60,7 @@ def test_bpe_ids_match_the_reference_fixture(tmp_path):
     assert tok.decode(tok.encode("a photo of a cat")).strip() == "a photo of a cat"
 
 
-@pytest.mark.skipif(not R.reference_available(), reason="reference checkout not present")
 def test_bpe_fuzz_against_the_live_reference(tmp_path):
-    R.install_shims()
-    from easynlp.modelzoo.models.clip.openclip_tokenizer import SimpleTokenizer as RefTok
+    """the reference SimpleTokenizer's encoder and its ids for every text of fuzz_texts(), as digests (tools/make_golden_fuzz.py)"""
     g, path, mine = _tok(tmp_path)
-    ref = RefTok(bpe_path=path)
-    assert ref.encoder == mine.encoder
-    rnd = random.Random(3)
-    words = ["photo", "photograph", "cat", "dogs", "the", "red", "running", "it's", "they've", "I'M", "café", "中文", "猫图", "2023",
-             "100%", "&amp;", "&lt;b&gt;", "<start_of_text>", "<END_OF_TEXT>", "\U0001F600", "a_b-c", "...", "½", "x" * 30, "\t", "\n", "  "]
-    for _ in range(3000):
-        t = " ".join(rnd.choice(words) for _ in range(rnd.randint(0, 12)))
-        if rnd.random() < 0.3:
-            t = "".join(rnd.choice("abcdefghij klmno'.,!?-_#中文é\t") for _ in range(rnd.randint(0, 30)))
-        assert ref.encode(t) == mine.encode(t), repr(t)
+    R.check_fuzz("openclip_bpe", [[t, mine.encode(t)] for t in fuzz_texts()], table=mine.encoder)

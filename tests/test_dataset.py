@@ -215,14 +215,11 @@ def test_clipapp_forward_takes_dataset_batches(tmp_path):
     assert torch.equal(a["logits_per_text"], b["logits_per_text"]) and torch.equal(a["image_embeds"], b["image_embeds"])
 
 
-def test_parse_row_by_schema_fuzz_against_the_reference():
-    from oracle import ref_harness as R
-    if not R.reference_available():
-        pytest.skip("reference checkout not present")
-    R.install_shims()
+def parse_row_cases():
+    """the seeded (row, schema) fuzz corpus: str / int / float columns of length 1 or 3, a surplus or a missing column, a trailing newline"""
     import random
-    from easynlp.utils import parse_row_by_schema as ref_parse
     rnd = random.Random(4)
+    cases = []
     for _ in range(500):
         ncol = rnd.randint(1, 4)
         schema, fields = [], []
@@ -237,38 +234,51 @@ def test_parse_row_by_schema_fuzz_against_the_reference():
         extra = rnd.choice([0, 0, 1, -1])                       # a surplus column, or one column short
         row_fields = fields + ["zz"] if extra == 1 else (fields[:-1] if extra == -1 and ncol > 1 else fields)
         row = "\t".join(row_fields) + rnd.choice(["", "\n"])
-        assert parse_row_by_schema(row, ",".join(schema)) == ref_parse(row, ",".join(schema)), (row, schema)
+        cases.append([row, ",".join(schema)])
+    return cases
 
 
-def test_wordpiece_loader_fuzz_against_the_reference_tokenizer(tmp_path):
-    """load_wordpiece_tokenizer (the installed transformers' BertTokenizer, 4.x or 5.x) vs the reference's vendored
-    BertTokenizer.from_pretrained(vocab.txt) (data.py:229) with the dataset's call (padding / truncation / max_length):
-    control characters, CJK, accents, full-width forms, 100-character words, special tokens inside the text."""
-    from oracle import ref_harness as R
-    if not R.reference_available():
-        pytest.skip("reference checkout not present")
-    R.install_shims()
+def wordpiece_texts():
+    """the seeded text corpus of the word-piece loader: control characters, CJK, accents, full-width forms, 100-150 character words,
+    special tokens inside the text"""
     import random
-    from easynlp.modelzoo import BertTokenizer as RefTok
-    from easynlp_amd.appzoo.clip.data import load_wordpiece_tokenizer
-    g = np.load(os.path.join(os.path.dirname(GOLD), "wukong_dataset_b5.npz"))          # BERT-layout vocabulary
-    vp = os.path.join(str(tmp_path), "vocab.txt")
-    with open(vp, "wb") as f:
-        f.write(g["vocab"].tobytes() + b"\n")
-    ref, mine = RefTok.from_pretrained(vp), load_wordpiece_tokenizer(vp)
     rnd = random.Random(11)
     alphabet = list("abcdefghijklmnopqrstuvwxyzABCXYZ  \t,.;:!?'\"-_()[]{}<>@#$%^&*+=~`|\\/0123456789") + \
         list("中文猫狗图的了，。！？「」·—…éÀüñçøßÆ") + ["​", "�", "\x07", " ", "　", "́", "\U0001F600", "\U00020000", "ａ", "①", "ｶ", "ﾞ", "ก", "ั"]
+    texts = []
     for it in range(1500):
         t = "".join(rnd.choice(alphabet) for _ in range(rnd.randint(0, 40)))
         if it % 40 == 0:
             t += "x" * rnd.choice([99, 100, 101, 150])
         if it % 55 == 0:
             t += " [SEP] [CLS] [MASK] [UNK] [PAD]"
-        a = ref([t], padding="max_length", truncation=True, max_length=24, return_tensors="pt")
-        b = mine([t], padding="max_length", truncation=True, max_length=24, return_tensors="pt")
-        for k in ("input_ids", "token_type_ids", "attention_mask"):
-            assert a[k].tolist() == b[k].tolist(), (k, t)
+        texts.append(t)
+    return texts
+
+
+def wordpiece_encode(tok, t):
+    """the dataset's call (data.py:229): [input_ids, token_type_ids, attention_mask] of one text"""
+    b = tok([t], padding="max_length", truncation=True, max_length=24, return_tensors="pt")
+    return [b[k].tolist() for k in ("input_ids", "token_type_ids", "attention_mask")]
+
+
+def test_parse_row_by_schema_fuzz_against_the_reference():
+    """parse_row_by_schema against the reference's easynlp.utils.parse_row_by_schema on parse_row_cases(): digests of its results
+    (tools/make_golden_fuzz.py)"""
+    R.check_fuzz("parse_row", [[c, parse_row_by_schema(*c)] for c in parse_row_cases()])
+
+
+def test_wordpiece_loader_fuzz_against_the_reference_tokenizer(tmp_path):
+    """load_wordpiece_tokenizer (the installed transformers' BertTokenizer, 4.x or 5.x) vs the reference's vendored
+    BertTokenizer.from_pretrained(vocab.txt) (data.py:229) with the dataset's call (padding / truncation / max_length) on
+    wordpiece_texts(): digests of the reference's input_ids / token_type_ids / attention_mask (tools/make_golden_fuzz.py)."""
+    from easynlp_amd.appzoo.clip.data import load_wordpiece_tokenizer
+    g = np.load(os.path.join(os.path.dirname(GOLD), "wukong_dataset_b5.npz"))          # BERT-layout vocabulary
+    vp = os.path.join(str(tmp_path), "vocab.txt")
+    with open(vp, "wb") as f:
+        f.write(g["vocab"].tobytes() + b"\n")
+    mine = load_wordpiece_tokenizer(vp)
+    R.check_fuzz("wordpiece", [[t, wordpiece_encode(mine, t)] for t in wordpiece_texts()])
 
 
 def test_webdataset_tar_input(tmp_path):

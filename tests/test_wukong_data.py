@@ -1,7 +1,7 @@
 """Input side of the Wukong application: the drop-in FullTokenizer / WukongCLIPDataset / WukongCLIPPredictor against the
 reference's own (appzoo/wukong_clip/{bert_tokenizer,data,predictor}.py).  Fixture tests/golden/wukong_dataset_b5.npz
-(tools/make_golden.py: run_wukong_dataset_case) = what the REFERENCE dataset and tokenizer produced; a live fuzz comparison
-runs when the checkout is present."""
+(tools/make_golden.py: run_wukong_dataset_case) = what the REFERENCE dataset and tokenizer produced; the reference tokenizer's
+output on a fuzz corpus is pinned by digests in tests/golden/reference_fuzz.json (tools/make_golden_fuzz.py)."""
 import base64
 import hashlib
 import io
@@ -48,23 +48,26 @@ def test_tokenizer_matches_the_reference_on_the_edge_case_corpus(tmp_path):
     assert ids[1].tolist() == [101, 102] + [0] * 30 and int(ids[2][31]) == 102 and int((ids[2] == 102).sum()) == 1
 
 
-@pytest.mark.skipif(not R.reference_available(), reason="reference checkout not present")
-def test_tokenizer_fuzz_against_the_live_reference(tmp_path):
-    R.install_shims()
-    from easynlp.appzoo.wukong_clip.bert_tokenizer import FullTokenizer as RefTok
-    g, d = _materialise(tmp_path)
-    vp = os.path.join(d, "vocab.txt")
-    ref, mine = RefTok(vocab_file=vp), FullTokenizer(vp)
-    assert ref.vocab == mine.vocab
+def fuzz_texts():
+    """the seeded fuzz corpus: ASCII, CJK, accents, control / zero-width / combining / full-width characters, 100-250 character words"""
     rnd = random.Random(11)
     alphabet = list("abcdefghijklmnopqrstuvwxyzABCXYZ  \t\n,.;:!?'\"-_()[]{}<>@#$%^&*+=~`|\\/0123456789") + \
         list("中文猫狗图的了，。！？「」·—…éÀüñçøßÆ") + ["​", "�", "\x00", "\x07", " ", "　", "́", " ",
                                               "\U0001F600", "\U00020000", "ａ", "①", "々", "〇", "ｶ", "ﾞ", "ก", "ั"]
+    texts = []
     for it in range(4000):
         t = "".join(rnd.choice(alphabet) for _ in range(rnd.randint(0, 40)))
         if it % 50 == 0:
             t += "x" * rnd.choice([99, 100, 101, 199, 200, 201, 250])
-        assert ref.tokenize(t) == mine.tokenize(t), repr(t)
+        texts.append(t)
+    return texts
+
+
+def test_tokenizer_fuzz_against_the_live_reference(tmp_path):
+    """the reference FullTokenizer's vocabulary and its tokens for every text of fuzz_texts(), as digests (tools/make_golden_fuzz.py)"""
+    g, d = _materialise(tmp_path)
+    mine = FullTokenizer(os.path.join(d, "vocab.txt"))
+    R.check_fuzz("wukong_tokenizer", [[t, mine.tokenize(t)] for t in fuzz_texts()], table=mine.vocab)
 
 
 def test_dataset_tokens_equal_the_reference_batch(tmp_path):

@@ -85,6 +85,37 @@ def test_bench_prints_one_contract_line():
         assert tel["source"] and (tel["samples"] == 0 or (100 < tel["shader_clock_mhz_mean"] < 3000 and 50 < tel["socket_power_w_mean"] < 2000))
 
 
+def test_bench_dump_outputs_are_what_the_last_timed_step_returned(tmp_path):
+    """`--dump-outputs DIR`: after the timed steps, DIR/<name>.npy holds what the last of them handed its caller.  Fused forward:
+    the loss -- warm-up 1 + 4 timed steps over the 4 rotated batches end on batch 0, the batch whose loss the line reports and the
+    oracle computes -- and the same arrays from a second run with the same arguments.  Autograd training step: forward()'s outputs,
+    the loss and a sample of every parameter gradient, float32, within 64 MiB."""
+    import numpy as np
+
+    def arrays(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    outs = [_run("--no-also", "--no-recall", "--sustained-steps", "0", "--steps", "4", "--dump-outputs", d) for d in dirs]
+    a, b = arrays(dirs[0]), arrays(dirs[1])
+    assert outs[0]["steps"] == 4 and outs[0]["dump_outputs"]["files"] == 1 and list(a) == ["loss"], (outs[0], list(a))
+    assert a["loss"].dtype == np.float32 and a["loss"].shape == ()
+    assert abs(float(a["loss"]) - outs[0]["loss"]) < 1e-4, (float(a["loss"]), outs[0]["loss"])
+    assert abs(float(a["loss"]) - _oracle_loss(64)) < 5e-3
+    assert list(b) == list(a) and all(np.array_equal(a[k], b[k]) for k in a)
+
+    d = str(tmp_path / "train")
+    out = _run("--no-also", "--no-recall", "--sustained-steps", "0", "--workload", "bf16_b1024_train_autograd", "--dump-outputs", d)
+    t = arrays(d)
+    assert {"loss", "logits_per_text", "logits_per_image", "image_embeds", "text_embeds"} <= set(t), sorted(t)
+    assert t["logits_per_text"].shape == (64, 64) and t["image_embeds"].shape == (64, 512) and t["loss"].shape == ()
+    assert np.array_equal(t["logits_per_image"], t["logits_per_text"].T)
+    grads = [k for k in t if k.startswith("grad.")]
+    assert "grad.chinese_clip.text_projection" in grads and len(grads) == out["dump_outputs"]["files"] - 5 > 100
+    assert all(t[k].dtype == np.float32 and np.isfinite(t[k]).all() for k in t)
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 << 20
+
+
 def test_recall_leg_agrees_with_the_oracle_evaluator():
     """the bench line's `recall_at_1` (fused similarity + rank kernel on the bf16 HIP path's embeddings) against `recall_at_1_oracle` (the
     reference evaluator's full-sort arithmetic on the fp32 CPU oracle's embeddings of the SAME trained weights): within 1e-3 (north star)"""
