@@ -36,27 +36,6 @@ __device__ __forceinline__ uint2 tr4(const char* p) {
 
 __device__ __forceinline__ int swz_f(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
 
-// -DEZ_ATTN_BWD_TRACE (tools/build_variants.py; never in the shipped library): every wave of attn_bwd_short_kernel writes the shader-clock
-// time of its phase boundaries -- entry, images landed, D / lse published, end of pass A, end of pass B, exit -- plus its HW_ID and the
-// 100 MHz real-time counter at entry and exit into a device array; tools/attn_bwd_trace.py reads it back (ezclip_dbg_attn_trace).
-#ifdef EZ_ATTN_BWD_TRACE
-constexpr int kTraceWords = 10, kTraceWgs = 16384, kTraceWaves = 9;
-__device__ unsigned long long g_attn_trace[(size_t)kTraceWgs * kTraceWaves * kTraceWords];
-#define EZ_TRACE(slot)                                                                                             \
-  do {                                                                                                             \
-    const int wg_ = blockIdx.y * gridDim.x + blockIdx.x;                                                           \
-    if (lane == 0 && wg_ < kTraceWgs) g_attn_trace[((size_t)wg_ * kTraceWaves + wave) * kTraceWords + (slot)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-#define EZ_TRACE_AUX(slot, value)                                                                                  \
-  do {                                                                                                             \
-    const int wg_ = blockIdx.y * gridDim.x + blockIdx.x;                                                           \
-    if (lane == 0 && wg_ < kTraceWgs) g_attn_trace[((size_t)wg_ * kTraceWaves + wave) * kTraceWords + (slot)] = (value); \
-  } while (0)
-#else
-#define EZ_TRACE(slot) do { } while (0)
-#define EZ_TRACE_AUX(slot, value) do { } while (0)
-#endif
-
 __device__ __forceinline__ void dma_rows_f(char* dst, const char* gbase, int64_t rs, int nrows, int L, int wave, int nwaves, int lane) {
   const int ninst = nrows / 8;
   for (int inst = wave; inst < ninst; inst += nwaves) {
@@ -97,19 +76,8 @@ __device__ __forceinline__ uint4 vec_frag(const float* x, int u, int h, int l31)
 //   dV = (P o M s)^T dO,   dP = (dO V^T) o M s,   dS = P o (dP - D) with the same D = <dO, O>,
 // pass A reads one 32-key word per tile for its query, pass B the words of a tile's 32 queries through a wave-private LDS
 // area (bit = its key), and the rows of P o M s no longer sum to one: sum_k dV[k] = dO^T rowsum(P o M s).
-#ifndef EZ_ATTN_BWD_LB
-#define EZ_ATTN_BWD_LB 576
-#endif
-#ifndef EZ_ATTN_BWD_UNROLL
-#define EZ_ATTN_BWD_UNROLL 1
-#endif
-#ifdef EZ_ATTN_BWD_PRIO
-#define EZ_PRIO(x) __builtin_amdgcn_s_setprio(x)
-#else
-#define EZ_PRIO(x) do { } while (0)
-#endif
 template <bool HAS_KB, bool CAUSAL, bool DROP>
-__global__ __launch_bounds__(DROP ? 512 : EZ_ATTN_BWD_LB) void attn_bwd_short_kernel(AttnBwdArgs a, int nt, int ra) {
+__global__ __launch_bounds__(DROP ? 512 : 576) void attn_bwd_short_kernel(AttnBwdArgs a, int nt, int ra) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const AttnArgs& f = a.f;
   const int head = blockIdx.x, b = blockIdx.y;
@@ -119,10 +87,6 @@ __global__ __launch_bounds__(DROP ? 512 : EZ_ATTN_BWD_LB) void attn_bwd_short_ke
   const int h = lane >> 5, l31 = lane & 31;
   const int nwaves = nt;      // 64 * nt threads (nt of the launch: the longest sample's tiles): no idle waves holding registers
   const int keep_words = nt;  // (words per (row, head) of AttnArgs::keep_bits)
-  EZ_TRACE(0);
-  EZ_TRACE_AUX(6, (unsigned long long)__builtin_amdgcn_s_getreg(((32 - 1) << 11) | 4) |       // HW_ID (hwreg 4), XCC_ID (hwreg 20) above it
-                      ((unsigned long long)__builtin_amdgcn_s_getreg(((32 - 1) << 11) | 20) << 32));
-  EZ_TRACE_AUX(7, __builtin_amdgcn_s_memrealtime());
   // packed batches (AttnArgs::cu / lens): rows cu[b] .. cu[b] + lens[b] - 1; nt (launch, LDS layout) is the longest sample's
   const int L = f.lens ? f.lens[b] : f.L, LKP = 32 * nt;
   const int64_t row0 = f.cu ? (int64_t)f.cu[b] : (int64_t)b * f.L;
@@ -170,9 +134,7 @@ __global__ __launch_bounds__(DROP ? 512 : EZ_ATTN_BWD_LB) void attn_bwd_short_ke
     if (row < L) lse_q = f.lse[((int64_t)b * f.H + head) * f.L + row];
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  EZ_TRACE(9);                                   // (this wave's own loads have landed; the barrier waits for the others')
   __syncthreads();
-  EZ_TRACE(1);
 
   const int fl = swz_f(l31);                     // (32t + l31 has the same f as l31)
   uint32_t roff[4];                              // row fragments: row l31 of a 32-row tile, chunk (2s+h) ^ f
@@ -232,7 +194,6 @@ __global__ __launch_bounds__(DROP ? 512 : EZ_ATTN_BWD_LB) void attn_bwd_short_ke
     if (h == 0) { lseA[row] = -lse_q * kLog2e; dA[row] = row < L ? -d_q : 0.f; }     // dA holds -D: pass B starts dP from it
   }
   __syncthreads();
-  EZ_TRACE(2);
   const float scale = f.scale;
   const float c = scale * kLog2e;
   const float nlse_q = -lse_q * kLog2e;
@@ -257,13 +218,11 @@ __global__ __launch_bounds__(DROP ? 512 : EZ_ATTN_BWD_LB) void attn_bwd_short_ke
       for (int r = 0; r < 16; ++r) sacc[r] = pacc[r] = 0.f;
       const char* kt = imgK + t * 4096;
       const char* vt = imgV + t * 4096;
-      EZ_PRIO(1);
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         mma32(sacc, *reinterpret_cast<const uint4*>(kt + roff[s]), xf[s], bf16_t());     // S^T[key][q]
         mma32(pacc, *reinterpret_cast<const uint4*>(vt + roff[s]), gf[s], bf16_t());     // dP^T[key][q]
       }
-      EZ_PRIO(0);
       uint32_t kwh = 0;
       if (DROP) {
         kwh = kw_next >> (4 * h);                       // bit 8 qd + e: key 8 qd + 4 h + e of this tile
@@ -300,17 +259,15 @@ __global__ __launch_bounds__(DROP ? 512 : EZ_ATTN_BWD_LB) void attn_bwd_short_ke
         dc.y = pack_bf16x2(ds[8 * u + 2], ds[8 * u + 3]);
         dc.z = pack_bf16x2(ds[8 * u + 4], ds[8 * u + 5]);
         dc.w = pack_bf16x2(ds[8 * u + 6], ds[8 * u + 7]);
-        EZ_PRIO(1);
         mma32(dq[0], tr_frag(kt, u, 0), dc, bf16_t());      // dQ^T[d][q] += K^T . dS^T
         mma32(dq[1], tr_frag(kt, u, 1), dc, bf16_t());
-        EZ_PRIO(0);
       }
     };
     if (HAS_KB || DROP) {
-#pragma unroll EZ_ATTN_BWD_UNROLL
+#pragma unroll 1
       for (int t = 0; t < nt; ++t) tile_a(t, std::true_type());
     } else {
-#pragma unroll EZ_ATTN_BWD_UNROLL
+#pragma unroll 1
       for (int t = 0; t < nt - 1; ++t) tile_a(t, std::false_type());
       tile_a(nt - 1, std::true_type());
     }
@@ -341,7 +298,6 @@ __global__ __launch_bounds__(DROP ? 512 : EZ_ATTN_BWD_LB) void attn_bwd_short_ke
       __builtin_amdgcn_wave_barrier();
     }
   }
-  EZ_TRACE(3);
   // ------------------------------------------------ pass B: dK, dV for keys 32*blk + l31 -----------------------
   if (active) {
 #pragma unroll
@@ -370,7 +326,7 @@ __global__ __launch_bounds__(DROP ? 512 : EZ_ATTN_BWD_LB) void attn_bwd_short_ke
       return f.keep_bits[((row0 + (qq < L ? qq : L - 1)) * f.H + head) * keep_words + blk];
     };
     uint32_t kwq_next = DROP ? keep_word_of(0) : 0u;
-#pragma unroll EZ_ATTN_BWD_UNROLL
+#pragma unroll 1
     for (int t = 0; t < nt; ++t) {
       f32x16_t sacc, pacc;
       if (DROP) {
@@ -390,13 +346,11 @@ __global__ __launch_bounds__(DROP ? 512 : EZ_ATTN_BWD_LB) void attn_bwd_short_ke
       for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
       const char* qt = imgQ + t * 4096;
       const char* gt = imgG + t * 4096;
-      EZ_PRIO(1);
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         mma32(sacc, *reinterpret_cast<const uint4*>(qt + roff[s]), xf[s], bf16_t());     // S[q][key]
         mma32(pacc, *reinterpret_cast<const uint4*>(gt + roff[s]), gf[s], bf16_t());     // dP[q][key] - D[q]
       }
-      EZ_PRIO(0);
       float p[16], ds[16];
 #pragma unroll
       for (int qd = 0; qd < 4; ++qd) {
@@ -432,12 +386,10 @@ __global__ __launch_bounds__(DROP ? 512 : EZ_ATTN_BWD_LB) void attn_bwd_short_ke
         pc.y = pack_bf16x2(p[8 * u + 2], p[8 * u + 3]);   dc.y = pack_bf16x2(ds[8 * u + 2], ds[8 * u + 3]);
         pc.z = pack_bf16x2(p[8 * u + 4], p[8 * u + 5]);   dc.z = pack_bf16x2(ds[8 * u + 4], ds[8 * u + 5]);
         pc.w = pack_bf16x2(p[8 * u + 6], p[8 * u + 7]);   dc.w = pack_bf16x2(ds[8 * u + 6], ds[8 * u + 7]);
-        EZ_PRIO(1);
         mma32(dv[0], tr_frag(gt, u, 0), pc, bf16_t());      // dV^T[d][key] += dO^T . P
         mma32(dv[1], tr_frag(gt, u, 1), pc, bf16_t());
         mma32(dk[0], tr_frag(qt, u, 0), dc, bf16_t());      // dK^T[d][key] += Q^T . dS
         mma32(dk[1], tr_frag(qt, u, 1), dc, bf16_t());
-        EZ_PRIO(0);
       }
     }
     if (row < L) {
@@ -462,7 +414,6 @@ __global__ __launch_bounds__(DROP ? 512 : EZ_ATTN_BWD_LB) void attn_bwd_short_ke
       bias_vec(imgK + blk * 4096, red_w + 384, scale, red_w);
     }
   }
-  EZ_TRACE(4);
   if (want_db) {      // combine the waves in a fixed order; per-sample partials (12k workgroups hammering 2304 addresses
     // with atomics cost more than the pass over dqkv this replaces), summed over the batch afterwards.  The barrier orders
     // LDS only: __syncthreads() would also wait out the dk / dv stores (vmcnt(0)).
@@ -474,8 +425,6 @@ __global__ __launch_bounds__(DROP ? 512 : EZ_ATTN_BWD_LB) void attn_bwd_short_ke
       a.db_part[((int64_t)b * 3 + (i >> 6)) * (f.H * 64) + head * 64 + (i & 63)] = s;
     }
   }
-  EZ_TRACE(5);
-  EZ_TRACE_AUX(8, __builtin_amdgcn_s_memrealtime());
 }
 
 
@@ -938,9 +887,3 @@ int attention_bwd_short(const AttnBwdArgs& a, hipStream_t stream) {
 
 }  // namespace ezclip
 
-#ifdef EZ_ATTN_BWD_TRACE
-extern "C" int ezclip_dbg_attn_trace(void* host, size_t bytes) {
-  const size_t all = sizeof(ezclip::g_attn_trace);
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(ezclip::g_attn_trace), bytes < all ? bytes : all, 0, hipMemcpyDeviceToHost);
-}
-#endif

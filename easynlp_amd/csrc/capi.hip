@@ -531,19 +531,22 @@ int ezclip_op_conv3x3_nhwc(const void* x, int b, int h, int w, int cp, const voi
 }
 
 int ezclip_debug_set(int key, int value) {
-  if (key == 0) { set_gemm_variant(value); return EZ_OK; }
+  if (key == 0) return set_gemm_variant(value);
   if (key == 1) { set_attention_variant(value); return EZ_OK; }
   if (key == 2) { set_fold_layernorm(value); return EZ_OK; }
   if (key == 3) { set_cls_last(value); return EZ_OK; }
   if (key == 4) { set_cls_last_train(value); return EZ_OK; }
   if (key == 5) { set_device_resample_tables(value); return EZ_OK; }
-  if (key == 6) { set_gemm_raster(value); return EZ_OK; }
+  if (key == 6) return set_gemm_raster(value);
   if (key == 7) { set_fuse_bert_qkv(value); return EZ_OK; }
   if (key == 8) { set_cls_q_only(value); return EZ_OK; }
   if (key == 9) { set_attention_short_tail(value); return EZ_OK; }
   if (key == 10) { set_rn_buffer_bound_mib(value); return EZ_OK; }
   if (key == 11) { set_attention_bwd_once(value); return EZ_OK; }
-  if (key == 12) { set_gemm_dephase(value); return EZ_OK; }
+  if (key == 12) {   // de-phasing of the persistent GEMM's workgroups: measured and removed; "off" is still accepted
+    EZ_REQUIRE(value == 0 || value == -1, "ezclip_debug_set(12, %d): GEMM workgroup de-phasing was removed; only 0 / -1 (off) are accepted", value);
+    return EZ_OK;
+  }
   set_error("ezclip_debug_set: unknown key %d", key);
   return EZ_ERR_INVALID;
 }
@@ -574,8 +577,10 @@ int ezclip_op_gemm_nt_ex(const ezclip_gemm_desc* d, void* stream) {
   const int fk = d->force_kernel;
   EZ_REQUIRE(fk == -1 || fk == 0 || fk == 2 || fk == 24, "ezclip_op_gemm_nt_ex: force_kernel %d", fk);
   if (fk >= 2) EZ_REQUIRE(gemm_nt_8p_eligible(g, d->dtype), "ezclip_op_gemm_nt_ex: the 8-phase kernel does not take this problem");
-  set_gemm_variant(fk);
+  set_gemm_variant(fk == 24 ? 2 : fk);
+  set_gemm8p_tile_per_workgroup(fk == 24);
   const int rc = gemm_nt(g, d->dtype, S(stream));
+  set_gemm8p_tile_per_workgroup(false);
   set_gemm_variant(-1);
   return rc;
 }

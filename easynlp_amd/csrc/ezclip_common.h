@@ -193,10 +193,6 @@ __device__ __forceinline__ void mma32(f32x16_t& acc, const uint4& a, const uint4
 // nothing but MFMAs on random register operands sustains 1.80 PFLOP/s (1.72 GHz) with 32x32x16 and 2.10 PFLOP/s (2.00 GHz) with
 // 16x16x32, 2.4 with either on all-zero operands (tools/mfma_power_probe.hip, profiles/r4_mfma_shape_power_probe.log).  It is
 // also the instruction of hipBLASLt's 256 x 256 x 64 kernel (profiles/r4_vendor_vs_ours_pmc.md).
-// EZ_MI16 = 0 rebuilds the bf16 GEMM kernels on 32x32x16 for A/B runs (tools/build_variants.py).
-#ifndef EZ_MI16
-#define EZ_MI16 1
-#endif
 __device__ __forceinline__ void mma16(f32x4_t& acc, const uint4& a, const uint4& b) {
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
 }

@@ -137,9 +137,9 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN * 64 == 256) ? 2 : 2) void g
   const char* gB = reinterpret_cast<const char*>(p.B);
   const int64_t lda_b = p.lda * (int64_t)sizeof(T), ldb_b = p.ldb * (int64_t)sizeof(T);
 
-  // bf16: v_mfma_f32_16x16x32_bf16 (EZ_MI16; the accumulation order of the 8-phase kernel, which stays bit-identical to this one);
+  // bf16: v_mfma_f32_16x16x32_bf16 (the accumulation order of the 8-phase kernel, which stays bit-identical to this one);
   // f32: v_mfma_f32_32x32x2_f32
-  constexpr bool MI16 = (EZ_MI16 != 0) && std::is_same<T, bf16_t>::value;
+  constexpr bool MI16 = std::is_same<T, bf16_t>::value;
   f32x16_t acc[MI16 ? 1 : TI][MI16 ? 1 : TJ];
   f32x4_t acc16[MI16 ? 2 * TI : 1][MI16 ? 2 * TJ : 1];
   if constexpr (MI16) {
@@ -401,10 +401,10 @@ int launch_nt(const GemmArgs& p, hipStream_t stream) {
 
 }  // namespace
 
-void set_gemm8p_ablate(int v);
-void set_gemm_variant(int v) {   // 2x = 8-phase kernel with ablation code x (timing experiments)
-  if (v >= 20 && v < 30) { set_gemm8p_ablate(v - 20); v = 2; } else set_gemm8p_ablate(0);
+int set_gemm_variant(int v) {
+  EZ_REQUIRE(v >= -1 && v <= 3, "ezclip_debug_set(0, %d): the GEMM kernel is -1 (heuristic), 0, 1, 2 or 3", v);
   g_gemm_variant = v;
+  return EZ_OK;
 }
 
 // true when gemm_nt would run this product on the 8-phase kernel (callers that want its optional extras -- folded

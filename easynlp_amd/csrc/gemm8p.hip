@@ -9,13 +9,13 @@
 // gemm.hip keeps the 128x128 kernel for f32, ragged N, tiny problems and f32 outputs.
 //
 // Structure (all sizes in bytes are per workgroup = per CU, 512 threads = 8 waves, 1 workgroup / CU):
-//   * waves 2 (M) x 4 (N); wave tile 128 x 64 = 4 x 2 MFMA 32x32 accumulators (128 fp32 registers);
-//     v_mfma_f32_32x32x16_bf16 issued with swapped operands, so a lane owns one M row and runs of 4
+//   * waves 2 (M) x 4 (N); wave tile 128 x 64 = 8 x 4 MFMA 16x16 accumulators (128 fp32 registers);
+//     v_mfma_f32_16x16x32_bf16 issued with swapped operands, so a lane owns one M row and runs of 4
 //     consecutive N.
 //   * A K-tile (64 k = 128 B per row) is split into four 16 KiB HALF-TILES of 128 rows each:
 //       A-lo / A-hi : rows the two wave rows read for their first / second 64 M rows,
 //       B-lo / B-hi : rows the four wave columns read for their first / second 32 N rows.
-//     The four quadrants of a wave tile are the four PHASES of a K-tile, 8 MFMAs each:
+//     The four quadrants of a wave tile are the four PHASES of a K-tile, 16 MFMAs each:
 //       P0 (A-lo,B-lo)  P1 (A-lo,B-hi)  P2 (A-hi,B-hi)  P3 (A-hi,B-lo)
 //     so LDS is read 12 / 4 / 8 / 0 fragments per phase and every half-tile's buffer is dead again
 //     after at most one phase.
@@ -90,61 +90,36 @@ __device__ __forceinline__ uint4 read_tr(const char* base) {
   return make_uint4(a.x, a.y, b.x, b.y);
 }
 
-// FR / ACC as in the NT kernel's phase(): Frags + f32x16_t[4][2] (32x32x16) or Frags16 + Acc16 (16x16x32, EZ_MI16).  MI16 fragments:
-// lane (column l15 of a 16-column block, k-quarter q4) wants m = 32 s + 8 q4 + 0..7 of its column: the two transpose reads of
+// Fragments and accumulators as in the NT kernel's phase() (Frags16 / Acc16, 16x16x32).  Lane (column l15 of a 16-column block,
+// k-quarter q4) wants m = 32 s + 8 q4 + 0..7 of its column: the two transpose reads of
 // read_tr at image row 32 s + 8 q4 (+ 4); 16-column block u of an A half sits 32 u bytes further along the image row -- bit 5 is
 // an immediate, bit 6 meets the row swizzle, hence two lane addresses (u < 2, u >= 2).
-template <int P, int PAR, bool ISSUE, int VM, typename FR, typename ACC>
-__device__ __forceinline__ void phase_tn(const CtxTN& c, FR& f, ACC& acc, uint32_t soff1,
+template <int P, int PAR, bool ISSUE, int VM>
+__device__ __forceinline__ void phase_tn(const CtxTN& c, Frags16& f, Acc16& acc, uint32_t soff1,
                                          uint32_t soff2) {
   constexpr int k8 = 4 * PAR + P;
-  constexpr bool MI16 = std::is_same<FR, Frags16>::value;
-  if constexpr (MI16) {
-    if constexpr (P == 0) {
-      constexpr int sB = ((k8 + 1) & 7) * kSlot, sA = (k8 & 7) * kSlot;
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int v = 0; v < 2; ++v) f.bl[v][s] = read_tr(c.smem + sB + (c.rdB ^ (uint32_t)(v << 5)) + s * 8192);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) f.a[u][s] = read_tr(c.smem + sA + (c.rdA[0] ^ (uint32_t)(u << 5)) + s * 8192);
-    } else if constexpr (P == 1) {
-      constexpr int sB = ((k8 + 1) & 7) * kSlot;
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int v = 0; v < 2; ++v) f.bh[v][s] = read_tr(c.smem + sB + (c.rdB ^ (uint32_t)(v << 5)) + s * 8192);
-    } else if constexpr (P == 2) {
-      constexpr int sA = ((k8 + 1) & 7) * kSlot;
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) f.a[u][s] = read_tr(c.smem + sA + (c.rdA[0] ^ (uint32_t)(u << 5)) + s * 8192);
-    }
-  } else {
   if constexpr (P == 0) {
     constexpr int sB = ((k8 + 1) & 7) * kSlot, sA = (k8 & 7) * kSlot;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) f.bl[s] = read_tr(c.smem + sB + c.rdB + s * 4096);
+    for (int s = 0; s < 2; ++s)
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      f.a[0][s] = read_tr(c.smem + sA + c.rdA[0] + s * 4096);
-      f.a[1][s] = read_tr(c.smem + sA + c.rdA[1] + s * 4096);
-    }
+      for (int v = 0; v < 2; ++v) f.bl[v][s] = read_tr(c.smem + sB + (c.rdB ^ (uint32_t)(v << 5)) + s * 8192);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) f.a[u][s] = read_tr(c.smem + sA + (c.rdA[0] ^ (uint32_t)(u << 5)) + s * 8192);
   } else if constexpr (P == 1) {
     constexpr int sB = ((k8 + 1) & 7) * kSlot;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) f.bh[s] = read_tr(c.smem + sB + c.rdB + s * 4096);
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int v = 0; v < 2; ++v) f.bh[v][s] = read_tr(c.smem + sB + (c.rdB ^ (uint32_t)(v << 5)) + s * 8192);
   } else if constexpr (P == 2) {
     constexpr int sA = ((k8 + 1) & 7) * kSlot;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      f.a[0][s] = read_tr(c.smem + sA + c.rdA[0] + s * 4096);
-      f.a[1][s] = read_tr(c.smem + sA + c.rdA[1] + s * 4096);
-    }
-  }
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) f.a[u][s] = read_tr(c.smem + sA + (c.rdA[0] ^ (uint32_t)(u << 5)) + s * 8192);
   }
   // soff1 / soff2: byte offset of the first row of K-tile t+1 / t+2 (per operand: A uses .x, B .y -- see caller)
   if constexpr (ISSUE) {
@@ -170,25 +145,15 @@ __device__ __forceinline__ void phase_tn(const CtxTN& c, FR& f, ACC& acc, uint32
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_setprio(1);
   constexpr int j = (P == 1 || P == 2) ? 1 : 0;
-  if constexpr (MI16) {
-    constexpr int rb0 = (P >= 2) ? 4 : 0, cb0 = 2 * j;
+  constexpr int rb0 = (P >= 2) ? 4 : 0, cb0 = 2 * j;
 #pragma unroll
-    for (int s = 0; s < 2; ++s)
+  for (int s = 0; s < 2; ++s)
 #pragma unroll
-      for (int v = 0; v < 2; ++v) {
-        const uint4& b = (j == 0) ? f.bl[v][s] : f.bh[v][s];
+    for (int v = 0; v < 2; ++v) {
+      const uint4& b = (j == 0) ? f.bl[v][s] : f.bh[v][s];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) mma16(acc.t[rb0 + u][cb0 + v], b, f.a[u][s]);
-      }
-  } else {
-    constexpr int i0 = (P >= 2) ? 2 : 0;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const uint4& b = (j == 0) ? f.bl[s] : f.bh[s];
-      mma32(acc[i0][j], b, f.a[0][s], bf16_t());
-      mma32(acc[i0 + 1][j], b, f.a[1][s], bf16_t());
+      for (int u = 0; u < 4; ++u) mma16(acc.t[rb0 + u][cb0 + v], b, f.a[u][s]);
     }
-  }
   __builtin_amdgcn_s_setprio(0);
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
@@ -199,8 +164,8 @@ __device__ __forceinline__ void phase_tn(const CtxTN& c, FR& f, ACC& acc, uint32
 // A offsets and the phases derive B's from the ratio-free pair below.
 struct KOff { uint32_t a1, a2, b1, b2; };
 
-template <int PAR, int TAIL, typename FR, typename ACC>
-__device__ __forceinline__ void ktile_tn(const CtxTN& c, FR& f, ACC& acc, const KOff& k) {
+template <int PAR, int TAIL>
+__device__ __forceinline__ void ktile_tn(const CtxTN& c, Frags16& f, Acc16& acc, const KOff& k) {
   // P0 issues B (t+1), P1 issues A (t+1), P2 issues A (t+2), P3 issues B (t+2)
   if constexpr (TAIL == 0) {
     phase_tn<0, PAR, true, 8>(c, f, acc, k.b1, 0);
@@ -226,7 +191,6 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm_tn_8p_kernel(GemmTNArgs p, 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 2, wn = wave & 3;
-  const int h = lane >> 5, l31 = lane & 31;
   const int id = xcd_remap(blockIdx.x, gridDim.x);
   const int split = id / ntiles, tile = id - split * ntiles;
   const int tp = tile / tiles_q, tq = tile - tp * tiles_q;
@@ -243,19 +207,14 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm_tn_8p_kernel(GemmTNArgs p, 
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int r = (wave * 2 + i) * 4 + (lane >> 4);                 // image row (m within the K-tile)
-#if EZ_MI16
     // 16x16x32 fragments: a 32-lane pass of the transpose read covers rows 8 q + {0..3} for TWO k-quarters q at one 32-byte column
     // block -- eight rows that must land on eight different 32-byte slots of the 256-byte bank row: the slot index is XORed with
     // f(m) = (m & 3) | ((m >> 3) & 1) << 2  (the 64-byte-granule swizzle of the 32x32x16 layout left rows m and m + 8 on the same banks:
     // two-way conflicts on every fragment read, 22-87 M conflict cycles per launch in profiles/r4_gemm_pmc.md before this)
     const uint32_t ch = (uint32_t)((lane & 15) ^ ((((r & 3) | (((r >> 3) & 1) << 2))) << 1)) << 4;
-#else
-    const uint32_t ch = (uint32_t)((lane & 15) ^ ((r & 3) << 2)) << 4;   // logical 16-byte chunk of the 256-byte row
-#endif
     c.voffA[i] = (m_begin + (uint32_t)r) * lda_b + (uint32_t)p0 * 2u + ch;
     c.voffB[i] = (m_begin + (uint32_t)r) * ldb_b + (uint32_t)q0 * 2u + ch;
   }
-#if EZ_MI16
   {
     const int t = lane & 15, q4 = lane >> 4;
     const int row = 8 * q4 + (t >> 2);                               // + 32*s + 4*kk via immediates (neither touches bits 0, 1, 3 of m)
@@ -266,7 +225,6 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm_tn_8p_kernel(GemmTNArgs p, 
     c.rdA[0] = (uint32_t)row * 256u + (colA ^ swz);
     c.rdA[1] = 0;
     c.rdB = (uint32_t)row * 256u + (colB ^ swz);
-    (void)h;
   }
   Acc16 acc;
 #pragma unroll
@@ -275,30 +233,6 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm_tn_8p_kernel(GemmTNArgs p, 
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc.t[i][j][r] = 0.f;
-  using FragsT = Frags16;
-#else
-  {
-    const int t = lane & 15, sub = (lane >> 4) & 1, g = h;
-    const int row = 8 * g + (t >> 2);                                // + 16*s + 4*kk via immediates
-    const uint32_t swz = (uint32_t)(t >> 2) << 6;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const uint32_t colb = (uint32_t)(wm * 64 + i * 32 + sub * 16 + (t & 3) * 4) * 2u;
-      c.rdA[i] = (uint32_t)row * 256u + (colb ^ swz);
-    }
-    const uint32_t colb = (uint32_t)(wn * 32 + sub * 16 + (t & 3) * 4) * 2u;
-    c.rdB = (uint32_t)row * 256u + (colb ^ swz);
-  }
-
-  f32x16_t acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  using FragsT = Frags;
-#endif
 
   const uint32_t stepA = 64u * lda_b, stepB = 64u * ldb_b;           // one K-tile further down
   {
@@ -322,7 +256,7 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm_tn_8p_kernel(GemmTNArgs p, 
     __builtin_amdgcn_sched_barrier(0);
   }
 
-  FragsT f;
+  Frags16 f;
   const int nk = kt_per_split;          // even, >= 4
   KOff k;
   k.a1 = stepA; k.a2 = 2 * stepA; k.b1 = stepB; k.b2 = 2 * stepB;
@@ -354,7 +288,6 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm_tn_8p_kernel(GemmTNArgs p, 
       *reinterpret_cast<float4*>(out + (size_t)(prow0 + rr) * (size_t)p.K + col) = v;
     }
   });
-  (void)l31;
 }
 
 // C = (accumulate ? C : 0) + sum_s part[s]   (fixed order)
@@ -409,32 +342,16 @@ bool gemm_nt_8p_eligible(const GemmArgs& p, int dtype) {
   return true;
 }
 
-int g_gemm8p_ablate = 0;
-void set_gemm8p_ablate(int v) { g_gemm8p_ablate = v; }
-#ifndef EZ_RASTER_GM_DEFAULT
-#define EZ_RASTER_GM_DEFAULT 106      // super-columns of 6 tile columns (gemm8p_nt.h tile_origin); identical to n-fastest order for N <= 1536
-#endif
-int g_gemm8p_raster = EZ_RASTER_GM_DEFAULT;
-void set_gemm_raster(int gm) { g_gemm8p_raster = gm < 0 ? EZ_RASTER_GM_DEFAULT : gm; }
-// De-phasing of the persistent workgroups (round 6; gemm8p_nt.h): workgroup b sleeps ((b >> 3) % period) * steps * 1024 shader clocks before
-// its first tile, so that the 32 CUs of an XCD enter their epilogues -- the C stream, with the matrix pipe idle -- at different times.
-// value = steps + 100 * period_code (period 32 / 2 / 4 / 8 / 16 for code 0..4); 0 = off; -1 = the built-in default (per shape, below).
-#ifndef EZ_DEPHASE_DEFAULT
-#define EZ_DEPHASE_DEFAULT 0
-#endif
-int g_gemm8p_dephase = -1;
-void set_gemm_dephase(int v) { g_gemm8p_dephase = v; }
-static int dephase_for(const GemmArgs& p, int tiles, int grid) {
-  if (tiles <= grid) return 0;                                  // a single round of tiles: nothing to stagger
-  if (g_gemm8p_dephase >= 0) return g_gemm8p_dephase;
-  // Measured (round 6, profiles/r6_gemm_dephase.md; gemm_bench, two repetitions, same box): stand-alone, the N = K = 768 products with many
-  // rounds of tiles gain 4 % from one step per CU of an XCD (vit.out+res 0.265 -> 0.253 ms, patch 0.228 -> 0.219 ms: their epilogue is the
-  // largest share of a tile), vit.qkv / vit.proj+res do not move, the three-round BERT products lose 2-3 %.  INSIDE the forward step the
-  // gain is gone: staggering every product costs 1.2 % (39.09 -> 39.55 ms), staggering only the N = K = 768 ones reads 39.30 vs 39.41 ms
-  // over three interleaved repetitions (the kernels of the two towers overlap on two streams and the staggered start is also a
-  // staggered end).  Off by default; ezclip_debug_set(12, v) / EZCLIP_GEMM_DEPHASE switch it on for A/B runs.
-  return EZ_DEPHASE_DEFAULT;
+constexpr int kRasterGmDefault = 106;   // super-columns of 6 tile columns (gemm8p_nt.h tile_origin); identical to n-fastest order for N <= 1536
+int g_gemm8p_raster = kRasterGmDefault;
+int set_gemm_raster(int gm) {
+  // 0: n-fastest, 1..99: super-rows of gm tile rows, 101..199: super-columns of gm - 100 tile columns (100 would be zero wide)
+  EZ_REQUIRE(gm >= -1 && gm < 200 && gm != 100, "ezclip_debug_set(6, %d): the tile order is -1 (default), 0..99 or 101..199", gm);
+  g_gemm8p_raster = gm < 0 ? kRasterGmDefault : gm;
+  return EZ_OK;
 }
+bool g_gemm8p_tile_per_wg = false;
+void set_gemm8p_tile_per_workgroup(bool on) { g_gemm8p_tile_per_wg = on; }
 
 namespace nt8p {
 EZ_8P_INSTANCES_A(EZ_8P_DECLARE)
@@ -451,9 +368,6 @@ int launch_8p_act(const GemmArgs& p, int tiles, int grid, hipStream_t stream) {
   constexpr bool plain = !R && !U && !C2 && !LN, has_none = plain || R || LN, has_gelu = plain || U || C2, has_qgelu = plain || U || C2 || LN;
   if constexpr (PS) return launch_8p<R, U, C2, LN, PS, ACT_NONE>(p, tiles, grid, stream);    // (row-stat partials: act none only, see eligibility)
   else {
-#ifdef EZ_8P_ACT_RUNTIME      // A/B build (tools/build_variants.py): every launch through the run-time-activation instantiation
-    return launch_8p<R, U, C2, LN, PS, kActRuntime>(p, tiles, grid, stream);
-#endif
     if (has_none && p.act == ACT_NONE) { if constexpr (has_none) return launch_8p<R, U, C2, LN, PS, ACT_NONE>(p, tiles, grid, stream); }
     if (has_qgelu && p.act == ACT_QUICKGELU) { if constexpr (has_qgelu) return launch_8p<R, U, C2, LN, PS, ACT_QUICKGELU>(p, tiles, grid, stream); }
     if (has_gelu && p.act == ACT_GELU_ERF) { if constexpr (has_gelu) return launch_8p<R, U, C2, LN, PS, ACT_GELU_ERF>(p, tiles, grid, stream); }
@@ -464,7 +378,6 @@ int launch_8p_act(const GemmArgs& p, int tiles, int grid, hipStream_t stream) {
 
 int gemm_nt_8p(const GemmArgs& p_in, hipStream_t stream) {
   GemmArgs p = p_in;
-  p.vec_ok = g_gemm8p_ablate;
   p.raster_gm = (p.N >> 8) > 1 ? g_gemm8p_raster : 0;
   if (g_num_cus == 0) {
     int dev = 0;
@@ -476,8 +389,7 @@ int gemm_nt_8p(const GemmArgs& p_in, hipStream_t stream) {
   const int tiles = ((p.M + 255) >> 8) * (p.N >> 8);
   int grid = tiles;                                         // one workgroup per CU (160 KiB LDS each)
   if (tiles > g_num_cus) grid = g_num_cus >= 8 ? (g_num_cus & ~7) : g_num_cus;   // multiple of 8: tile -> XCD affinity across rounds
-  if (g_gemm8p_ablate == 4) grid = tiles;                   // debugging: one tile per workgroup
-  p.raster_gm += 10000 * dephase_for(p, tiles, grid);        // (decoded by the kernel: GemmArgs has no room for another field, see kernels.h)
+  if (g_gemm8p_tile_per_wg) grid = tiles;                   // (ezclip_op_gemm_nt_ex force_kernel 24: no persistent loop)
   int rc;
   {
     ProfScope ps(PROF_GEMM, 2.0 * p.M * (double)p.N * p.K, stream);

@@ -11,13 +11,13 @@
 // gemm.hip keeps the 128x128 kernel for f32, ragged N, tiny problems and f32 outputs.
 //
 // Structure (all sizes in bytes are per workgroup = per CU, 512 threads = 8 waves, 1 workgroup / CU):
-//   * waves 2 (M) x 4 (N); wave tile 128 x 64 = 4 x 2 MFMA 32x32 accumulators (128 fp32 registers);
-//     v_mfma_f32_32x32x16_bf16 issued with swapped operands, so a lane owns one M row and runs of 4
+//   * waves 2 (M) x 4 (N); wave tile 128 x 64 = 8 x 4 MFMA 16x16 accumulators (128 fp32 registers);
+//     v_mfma_f32_16x16x32_bf16 issued with swapped operands, so a lane owns one M row and runs of 4
 //     consecutive N.
 //   * A K-tile (64 k = 128 B per row) is split into four 16 KiB HALF-TILES of 128 rows each:
 //       A-lo / A-hi : rows the two wave rows read for their first / second 64 M rows,
 //       B-lo / B-hi : rows the four wave columns read for their first / second 32 N rows.
-//     The four quadrants of a wave tile are the four PHASES of a K-tile, 8 MFMAs each:
+//     The four quadrants of a wave tile are the four PHASES of a K-tile, 16 MFMAs each:
 //       P0 (A-lo,B-lo)  P1 (A-lo,B-hi)  P2 (A-hi,B-hi)  P3 (A-hi,B-lo)
 //     so LDS is read 12 / 4 / 8 / 0 fragments per phase and every half-tile's buffer is dead again
 //     after at most one phase.
@@ -41,8 +41,6 @@
 //     tile are DMA'd while the current epilogue runs, bias / residual loads are issued one block ahead, and
 //     there is no workgroup launch, kernarg load or cold pipeline between tiles.
 #pragma once
-#include <type_traits>
-
 #include "ezclip_common.h"
 #include "kernels.h"
 #include "gemm_pipe.h"
@@ -62,77 +60,46 @@ struct Ctx {
 
 // One phase.  P: quadrant; PAR: tile parity (static slot bases); ISSUE: issue half-tile k+6;
 // VM: vmcnt to wait for afterwards (-1: none).
-// FR / ACC: Frags + f32x16_t[4][2] (v_mfma_f32_32x32x16_bf16: 8 per phase) or Frags16 + Acc16 (v_mfma_f32_16x16x32_bf16: 16 per
-// phase, EZ_MI16) -- same bytes out of LDS either way (8 / 4 ds_read_b128 per A / B half), same 256 matrix-pipe cycles.
-// FIRST (MI16 only): first K-tile of an output tile -- the first k-step's MFMAs take a literal zero as their C operand, so the
-// accumulators are never zeroed by VALU moves (128 v_mov per wave and tile in the 32x32x16 build) and carry no value from one
-// tile of the persistent loop into the next (each tile defines them afresh: no loop-carried register tuples to keep coalesced).
-template <int P, int PAR, bool ISSUE, int VM, int VMR = VM, int XLD = 0, bool FIRST = false, typename FR, typename ACC>
-__device__ __forceinline__ void phase(const Ctx& c, FR& f, ACC& acc, uint32_t kbyte_next1,
+// Fragments and accumulators of the 16x16x32 layout (Frags16 / Acc16, gemm_pipe.h): 16 v_mfma_f32_16x16x32_bf16 per phase,
+// 8 / 4 ds_read_b128 per A / B half, 256 matrix-pipe cycles.
+// FIRST: first K-tile of an output tile -- the first k-step's MFMAs take a literal zero as their C operand, so the
+// accumulators are never zeroed by VALU moves and carry no value from one tile of the persistent loop into the next (each
+// tile defines them afresh: no loop-carried register tuples to keep coalesced).
+template <int P, int PAR, bool ISSUE, int VM, int VMR = VM, int XLD = 0, bool FIRST = false>
+__device__ __forceinline__ void phase(const Ctx& c, Frags16& f, Acc16& acc, uint32_t kbyte_next1,
                                       uint32_t kbyte_next2, bool relaxed = false) {
   constexpr int k8 = 4 * PAR + P;                 // phase number mod 8
-  constexpr bool MI16 = std::is_same<FR, Frags16>::value;
   // ---- read segment -----------------------------------------------------------------------
-#ifdef EZ_ABL_NOLDSREAD     // timing ablation (results wrong by construction): fragments are read in the first K-tile of a tile only
-  constexpr bool kRead = FIRST;
-#else
-  constexpr bool kRead = true;
-#endif
-  if constexpr (!kRead) {
-  } else if constexpr (MI16) {
-    if constexpr (P == 0) {
-      constexpr int sB = ((k8 + 1) & 7) * kSlot, sA = (k8 & 7) * kSlot;
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int v = 0; v < 2; ++v) f.bl[v][s] = *reinterpret_cast<const uint4*>(c.smem + sB + v * 2048 + c.rdB[s]);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) f.a[u][s] = *reinterpret_cast<const uint4*>(c.smem + sA + u * 2048 + c.rdA[s]);
-    } else if constexpr (P == 1) {
-      constexpr int sB = ((k8 + 1) & 7) * kSlot;    // B-hi is half-tile 4t+2
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int v = 0; v < 2; ++v) f.bh[v][s] = *reinterpret_cast<const uint4*>(c.smem + sB + v * 2048 + c.rdB[s]);
-    } else if constexpr (P == 2) {
-      constexpr int sA = ((k8 + 1) & 7) * kSlot;    // A-hi is half-tile 4t+3
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) f.a[u][s] = *reinterpret_cast<const uint4*>(c.smem + sA + u * 2048 + c.rdA[s]);
-    }
-  } else {
   if constexpr (P == 0) {
     constexpr int sB = ((k8 + 1) & 7) * kSlot, sA = (k8 & 7) * kSlot;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) f.bl[s] = *reinterpret_cast<const uint4*>(c.smem + sB + c.rdB[s]);
+    for (int s = 0; s < 2; ++s)
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      f.a[0][s] = *reinterpret_cast<const uint4*>(c.smem + sA + c.rdA[s]);
-      f.a[1][s] = *reinterpret_cast<const uint4*>(c.smem + sA + 4096 + c.rdA[s]);
-    }
+      for (int v = 0; v < 2; ++v) f.bl[v][s] = *reinterpret_cast<const uint4*>(c.smem + sB + v * 2048 + c.rdB[s]);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) f.a[u][s] = *reinterpret_cast<const uint4*>(c.smem + sA + u * 2048 + c.rdA[s]);
   } else if constexpr (P == 1) {
     constexpr int sB = ((k8 + 1) & 7) * kSlot;    // B-hi is half-tile 4t+2
 #pragma unroll
-    for (int s = 0; s < 4; ++s) f.bh[s] = *reinterpret_cast<const uint4*>(c.smem + sB + c.rdB[s]);
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int v = 0; v < 2; ++v) f.bh[v][s] = *reinterpret_cast<const uint4*>(c.smem + sB + v * 2048 + c.rdB[s]);
   } else if constexpr (P == 2) {
     constexpr int sA = ((k8 + 1) & 7) * kSlot;    // A-hi is half-tile 4t+3
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      f.a[0][s] = *reinterpret_cast<const uint4*>(c.smem + sA + c.rdA[s]);
-      f.a[1][s] = *reinterpret_cast<const uint4*>(c.smem + sA + 4096 + c.rdA[s]);
-    }
-  }
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) f.a[u][s] = *reinterpret_cast<const uint4*>(c.smem + sA + u * 2048 + c.rdA[s]);
   }
   // ---- DMA for half-tile k+6 (kind (P+2)&3: P0 -> B-hi(t+1), P1 -> A-hi(t+1), P2 -> A-lo(t+2), P3 -> B-lo(t+2))
   if constexpr (ISSUE) {
     constexpr int slot = ((k8 + 6) & 7) * kSlot;
     const uint32_t dst = c.lds_base + slot + c.dma_dst;
     if constexpr (P == 0) {
-      dma16<1>(dst, c.voffB[0], c.srdB, kbyte_next1 + c.hiB);
-      dma16<1>(dst + 1024, c.voffB[1], c.srdB, kbyte_next1 + c.hiB);
+      dma16(dst, c.voffB[0], c.srdB, kbyte_next1 + c.hiB);
+      dma16(dst + 1024, c.voffB[1], c.srdB, kbyte_next1 + c.hiB);
     } else if constexpr (P == 1) {
       dma16(dst, c.voffA[0], c.srdA, kbyte_next1 + c.hiA);
       dma16(dst + 1024, c.voffA[1], c.srdA, kbyte_next1 + c.hiA);
@@ -140,14 +107,14 @@ __device__ __forceinline__ void phase(const Ctx& c, FR& f, ACC& acc, uint32_t kb
       dma16(dst, c.voffA[0], c.srdA, kbyte_next2);
       dma16(dst + 1024, c.voffA[1], c.srdA, kbyte_next2);
     } else {
-      dma16<1>(dst, c.voffB[0], c.srdB, kbyte_next2);
-      dma16<1>(dst + 1024, c.voffB[1], c.srdB, kbyte_next2);
+      dma16(dst, c.voffB[0], c.srdB, kbyte_next2);
+      dma16(dst + 1024, c.voffB[1], c.srdB, kbyte_next2);
     }
   }
   if constexpr (VMR != VM) {   // first K-tile of a tile: the previous tile's stores may still be queued (see ktile)
-    if (relaxed) wait_role<VM, VMR - VM, 0, true>(); else wait_role<VM, 0, 0, true>();
+    if (relaxed) wait_vm<VMR>(); else wait_vm<VM>();
   } else if constexpr (VM >= 0) {
-    wait_role<VM - XLD, 0, XLD, true>();
+    wait_vm<VM>();
   }
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
@@ -155,33 +122,23 @@ __device__ __forceinline__ void phase(const Ctx& c, FR& f, ACC& acc, uint32_t kb
   // ---- MFMA segment -------------------------------------------------------------------------
   __builtin_amdgcn_s_setprio(1);
   constexpr int j = (P == 1 || P == 2) ? 1 : 0;
-  if constexpr (MI16) {
-    constexpr int rb0 = (P >= 2) ? 4 : 0, cb0 = 2 * j;
+  constexpr int rb0 = (P >= 2) ? 4 : 0, cb0 = 2 * j;
 #pragma unroll
-    for (int s = 0; s < 2; ++s)
+  for (int s = 0; s < 2; ++s)
 #pragma unroll
-      for (int v = 0; v < 2; ++v) {
-        const uint4& b = (j == 0) ? f.bl[v][s] : f.bh[v][s];
+    for (int v = 0; v < 2; ++v) {
+      const uint4& b = (j == 0) ? f.bl[v][s] : f.bh[v][s];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (FIRST && s == 0) {
-            f32x4_t z = {0.f, 0.f, 0.f, 0.f};
-            mma16(z, b, f.a[u][s]);
-            acc.t[rb0 + u][cb0 + v] = z;
-          } else {
-            mma16(acc.t[rb0 + u][cb0 + v], b, f.a[u][s]);
-          }
+      for (int u = 0; u < 4; ++u) {
+        if (FIRST && s == 0) {
+          f32x4_t z = {0.f, 0.f, 0.f, 0.f};
+          mma16(z, b, f.a[u][s]);
+          acc.t[rb0 + u][cb0 + v] = z;
+        } else {
+          mma16(acc.t[rb0 + u][cb0 + v], b, f.a[u][s]);
         }
       }
-  } else {
-    constexpr int i0 = (P >= 2) ? 2 : 0;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const uint4& b = (j == 0) ? f.bl[s] : f.bh[s];
-      mma32(acc[i0][j], b, f.a[0][s], bf16_t());
-      mma32(acc[i0 + 1][j], b, f.a[1][s], bf16_t());
     }
-  }
   __builtin_amdgcn_s_setprio(0);
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
@@ -193,11 +150,11 @@ __device__ __forceinline__ void phase(const Ctx& c, FR& f, ACC& acc, uint32_t kb
 // VMR (with relaxed = true): the count for the first K-tile of a tile whose predecessor's stores are still in the
 // queue (they sit between this tile's half-tiles 0..5 and 6.. in issue order).
 // XL (TAIL == 2 only): loads of the epilogue's block 0 issued right before this last K-tile (newer than every DMA).
-template <int PAR, int TAIL, int VMR = 8, int XL = 0, typename FR, typename ACC>
-__device__ __forceinline__ void ktile(const Ctx& c, FR& f, ACC& acc, uint32_t kb1, uint32_t kb2,
+template <int PAR, int TAIL, int VMR = 8, int XL = 0>
+__device__ __forceinline__ void ktile(const Ctx& c, Frags16& f, Acc16& acc, uint32_t kb1, uint32_t kb2,
                                       bool relaxed = false) {
   if constexpr (TAIL == 0) {
-    constexpr bool FIRST = VMR != 8 && std::is_same<FR, Frags16>::value;     // (VMR != 8 marks the first K-tile of a tile)
+    constexpr bool FIRST = VMR != 8;      // (VMR != 8 marks the first K-tile of a tile)
     phase<0, PAR, true, 8, VMR, 0, FIRST>(c, f, acc, kb1, kb2, relaxed);
     phase<1, PAR, true, 8, VMR, 0, FIRST>(c, f, acc, kb1, kb2, relaxed);
     phase<2, PAR, true, 8, VMR, 0, FIRST>(c, f, acc, kb1, kb2, relaxed);
@@ -228,7 +185,6 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm_nt_8p_kernel(GemmArgs p, in
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 2, wn = wave & 3;
-  const int h = lane >> 5, l31 = lane & 31;
   const int tiles_n = p.N >> 8;
 
   Ctx c;
@@ -240,7 +196,6 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm_nt_8p_kernel(GemmArgs p, in
   c.hiA = 64u * lda_b;
   c.hiB = 32u * ldb_b;
   c.dma_dst = wave * 2048;
-#if EZ_MI16
   {   // 16x16x32 fragments: lane (row l15 of a 16-row block, k-quarter q4 of a 32-k step): chunk 4 s + q4; the swizzle (row >> 1) & 7
       // of row 16 u + l15 is (l15 >> 1) & 7 for every block u, so the blocks are plain + u * 2048 offsets
     const int l15 = lane & 15, q4 = lane >> 4;
@@ -252,25 +207,13 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm_nt_8p_kernel(GemmArgs p, in
       c.rdB[s] = (uint32_t)(wn * 32 + l15) * 128 + ch;
     }
     c.rdA[2] = c.rdA[3] = c.rdB[2] = c.rdB[3] = 0;
-    (void)h; (void)l31;
   }
-#else
-  {
-    const int sw = (l31 >> 1) & 7;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const uint32_t ch = (uint32_t)((2 * s + h) ^ sw) << 4;
-      c.rdA[s] = (uint32_t)(wm * 64 + l31) * 128 + ch;
-      c.rdB[s] = (uint32_t)(wn * 32 + l31) * 128 + ch;
-    }
-  }
-#endif
   // Tile order.  An XCD works on 32 consecutive logical tiles at a time (xcd_remap), and what its L2 has to fetch per
   // round is one A row panel per distinct tile row + one B panel per distinct tile column.  n-fastest order makes that
   // 32 / tiles_n rows + tiles_n columns (N = 3072: 2.7 + 12); with raster_gm = g the tiles of g consecutive tile rows are
   // walked column by column, so a round covers g rows x 32 / g columns (g = 4: 4 + 8) -- fewer panels through the fabric.
   const int tiles_m = (p.M + 255) >> 8;
-  const int raster_gm = p.raster_gm % 10000;        // (the launcher packs the de-phasing request above it)
+  const int raster_gm = p.raster_gm;
   auto tile_origin = [&](int v, int& m0, int& n0) {
     const int t = xcd_remap(v, ntiles);
     int tm, tn;
@@ -318,49 +261,26 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm_nt_8p_kernel(GemmArgs p, in
     const uint32_t d = c.lds_base + c.dma_dst;
     dma16(d + 0 * kSlot, c.voffA[0], c.srdA, 0);
     dma16(d + 0 * kSlot + 1024, c.voffA[1], c.srdA, 0);
-    dma16<1>(d + 1 * kSlot, c.voffB[0], c.srdB, 0);
-    dma16<1>(d + 1 * kSlot + 1024, c.voffB[1], c.srdB, 0);
-    dma16<1>(d + 2 * kSlot, c.voffB[0], c.srdB, c.hiB);
-    dma16<1>(d + 2 * kSlot + 1024, c.voffB[1], c.srdB, c.hiB);
+    dma16(d + 1 * kSlot, c.voffB[0], c.srdB, 0);
+    dma16(d + 1 * kSlot + 1024, c.voffB[1], c.srdB, 0);
+    dma16(d + 2 * kSlot, c.voffB[0], c.srdB, c.hiB);
+    dma16(d + 2 * kSlot + 1024, c.voffB[1], c.srdB, c.hiB);
     dma16(d + 3 * kSlot, c.voffA[0], c.srdA, c.hiA);
     dma16(d + 3 * kSlot + 1024, c.voffA[1], c.srdA, c.hiA);
     dma16(d + 4 * kSlot, c.voffA[0], c.srdA, 128);
     dma16(d + 4 * kSlot + 1024, c.voffA[1], c.srdA, 128);
-    dma16<1>(d + 5 * kSlot, c.voffB[0], c.srdB, 128);
-    dma16<1>(d + 5 * kSlot + 1024, c.voffB[1], c.srdB, 128);
+    dma16(d + 5 * kSlot, c.voffB[0], c.srdB, 128);
+    dma16(d + 5 * kSlot + 1024, c.voffB[1], c.srdB, 128);
   };
 
-  // De-phasing (gemm8p.hip set_gemm_dephase): the CUs of an XCD start their first tile ((b >> 3) % period) * steps * 1024 clocks apart
-  // and -- every tile taking the same time -- stay that far apart: their epilogues (the C stream, matrix pipe idle) no longer coincide.
-  {
-    const int dp = p.raster_gm / 10000;
-    if (dp > 0) {
-      const int code = dp / 100, steps = dp - code * 100;
-      const unsigned period = code == 0 ? 32u : (1u << code);
-      for (int d = (int)((blockIdx.x >> 3) % period) * steps; d > 0; --d) __builtin_amdgcn_s_sleep(16);
-    }
-  }
   const EpiCtx ep = make_epi_ctx<HAS_R, HAS_U, HAS_C2, HAS_LN, HAS_PS>(p);
   constexpr int NS = kStoresPerBlock * (1 + (HAS_C2 ? 1 : 0) + (HAS_PS ? 1 : 0));   // stores per 32-row block
   int v = blockIdx.x, m0, n0;
   tile_origin(v, m0, n0);
   set_tile(m0, n0);
   issue_prologue();
-  wait_role<8, 0, 0, true>();           // half-tiles 0 and 1 (this wave's pieces)
+  wait_vm<8>();                         // half-tiles 0 and 1 (this wave's pieces)
   bool first = true;
-
-#if EZ_MI16
-  using FragsT = Frags16;
-#else
-  f32x16_t acc[4][2];                   // (re-zeroed block by block in the epilogue)
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  using FragsT = Frags;
-#endif
 
   for (;;) {
     __builtin_amdgcn_sched_barrier(0);
@@ -368,10 +288,8 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm_nt_8p_kernel(GemmArgs p, in
     if (wm == 1) __builtin_amdgcn_s_barrier();   // wave row 1 runs one barrier behind
     __builtin_amdgcn_sched_barrier(0);
 
-    FragsT f;
-#if EZ_MI16
+    Frags16 f;
     Acc16 acc;                            // defined by the first K-tile's MFMAs (zero C operand): nothing carried between tiles
-#endif
     const int nk = p.K >> 6;              // even, >= 4 (checked by the launcher)
     uint32_t kb = 0;                      // byte offset of the current tile's k range
     // first K-tile: the previous tile's 4*NS stores may still be in flight between half-tiles 0..5 and 6..
@@ -418,7 +336,7 @@ __global__ __launch_bounds__(kThreads8, 2) void gemm_nt_8p_kernel(GemmArgs p, in
                                                     issue_prologue();
                                                   });
     if (!has_next) break;
-    wait_role<6, 4 * NS, 0, true>();   // half-tiles 0..2 of the next tile have landed; 3..5 and this tile's stores may still fly
+    wait_vm<6 + 4 * NS>();              // half-tiles 0..2 of the next tile have landed; 3..5 and this tile's stores may still fly
     first = false;
     v = vn; m0 = m0n; n0 = n0n;
   }

@@ -16,71 +16,17 @@ constexpr int kRing = 8 * kSlot;       // 128 KiB
 constexpr int kThreads8 = 512;
 
 // LDS-DMA: 64 lanes x 16 B land at lds_dst + lane*16 (wave-uniform destination).
-// EZ_ROLE_X / EZ_ROLE_Y (tools/build_variants.py; timing only, results are wrong by construction): is the store tail of the
-// epilogue the in-order vmcnt of the wave that also waits for the LDS-DMA, or the CU's memory pipeline?  In both variants wave
-// row 0 issues every DMA of the workgroup (its own pieces twice: same volume into LDS) and wave row 1 none; the C stores are
-// issued by wave row 1 only (X: the DMA waves never have a store in their queue) or by wave row 0 only (Y: they do).  Same
-// traffic, same instruction counts per CU -- X faster than Y means a role split would hide the tail.
-#if defined(EZ_ROLE_X) || defined(EZ_ROLE_Y)
-#define EZ_ROLES 1
-__device__ __forceinline__ bool ez_dma_role() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 8) == 0; }
-#ifdef EZ_ROLE_X
-__device__ __forceinline__ bool ez_store_role() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 8) == 1; }
-#else
-__device__ __forceinline__ bool ez_store_role() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 8) == 0; }
-#endif
-#else
-#define EZ_ROLES 0
-#endif
-
-// Cache-policy bits of the LDS-DMA loads, per operand (experiment hooks of tools/build_variants.py: -DEZ_DMA_A_MOD='" nt"' etc.; default none).
-#ifndef EZ_DMA_A_MOD
-#define EZ_DMA_A_MOD ""
-#endif
-#ifndef EZ_DMA_B_MOD
-#define EZ_DMA_B_MOD ""
-#endif
-template <int OPERAND>   // 0: A (activations: streamed once per column tile), 1: B (weights: re-read by every row tile)
-__device__ __forceinline__ void dma16_one(uint32_t lds_dst, uint32_t voff, const i32x4_t& srd, uint32_t soff) {
-  uint32_t keep;
-  if constexpr (OPERAND == 0) {
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %2, %3, %4 offen" EZ_DMA_A_MOD " lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "s"(lds_dst), "v"(voff), "s"(srd), "s"(soff)
-        : "memory");
-  } else {
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %2, %3, %4 offen" EZ_DMA_B_MOD " lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "s"(lds_dst), "v"(voff), "s"(srd), "s"(soff)
-        : "memory");
-  }
-}
-template <int OPERAND = 0>
 __device__ __forceinline__ void dma16(uint32_t lds_dst, uint32_t voff, const i32x4_t& srd, uint32_t soff) {
-#ifdef EZ_ABL_NODMA         // timing ablation (results wrong by construction): no global -> LDS traffic at all; the counted waits see an empty queue
-  asm volatile("" ::"s"(lds_dst), "v"(voff), "s"(soff));
-  return;
-#endif
-#ifdef EZ_ABL_DMASAME       // timing ablation: the same instruction stream, every DMA aimed at the first KiB of the operand (L1 / L2 hits:
-  voff &= 0x3f0u; soff = 0;  // issue cost and LDS writes stay, L2 / fabric / HBM traffic goes)
-#endif
-#if EZ_ROLES
-  if (!ez_dma_role()) return;
-  dma16_one<OPERAND>(lds_dst, voff, srd, soff);
-  dma16_one<OPERAND>(lds_dst + 8192u, voff, srd, soff);     // the partner wave's region of the half-tile image
-#else
-  dma16_one<OPERAND>(lds_dst, voff, srd, soff);
-#endif
+  uint32_t keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %1\n\t"
+      "s_nop 0\n\t"
+      "buffer_load_dwordx4 %2, %3, %4 offen lds\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "s"(lds_dst), "v"(voff), "s"(srd), "s"(soff)
+      : "memory");
 }
 
 // Lane id recomputed on the spot (v_mbcnt): an asm volatile cannot be hoisted out of the tile loop, so values
@@ -96,21 +42,6 @@ __device__ __forceinline__ void wait_vm() {
   if constexpr (N >= 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// Counted wait written as (DMAs, stores, other loads) that may stay in flight.  Without the role experiment: their sum.
-// MAIN: a wait of the main loop (for LDS-DMA only): waves that issue no DMA skip it.
-template <int ND, int NST, int NLD, bool MAIN>
-__device__ __forceinline__ void wait_role() {
-#if EZ_ROLES
-  if (ez_dma_role()) {
-    if (ez_store_role()) wait_vm<2 * ND + NST + NLD>(); else wait_vm<2 * ND + NLD>();
-  } else if (!MAIN) {
-    if (ez_store_role()) wait_vm<NST + NLD>(); else wait_vm<NLD>();
-  }
-#else
-  wait_vm<ND + NST + NLD>();
-#endif
-}
-
 __device__ __forceinline__ i32x4_t make_srd(const void* base, uint32_t bytes) {
   const uint64_t a = (uint64_t)base;
   i32x4_t r;
@@ -121,13 +52,7 @@ __device__ __forceinline__ i32x4_t make_srd(const void* base, uint32_t bytes) {
   return r;
 }
 
-struct Frags {
-  uint4 a[2][4];   // current A half: [i'][k-step]
-  uint4 bl[4];     // B-lo, kept from P0 to P3
-  uint4 bh[4];     // B-hi, kept from P1 to P2
-};
-
-// 16x16x32 layout of the same 128 x 64 wave tile (EZ_MI16): 8 x 4 accumulators of 16 x 16, fragments per 16 rows and 32 k
+// 16x16x32 layout of the 128 x 64 wave tile: 8 x 4 accumulators of 16 x 16, fragments per 16 rows and 32 k
 struct Frags16 {
   uint4 a[4][2];   // current A half: [16-row block][k-step of 32]
   uint4 bl[2][2];  // B-lo, kept from P0 to P3: [16-column block][k-step]
@@ -135,9 +60,6 @@ struct Frags16 {
 };
 struct Acc16 {
   f32x4_t t[8][4]; // [16-row block][16-column block]: lane (m = lane & 15, q = lane >> 4) holds columns 4 q .. 4 q + 3 of row m
-};
-struct Acc32 {
-  f32x16_t t[4][2];
 };
 
 template <int N, typename F>
@@ -209,12 +131,11 @@ __device__ __forceinline__ EpiCtx make_epi_ctx(const GemmArgs& p) {
   return e;
 }
 
-// Epilogue of one 128 x 64 wave tile (4 x 2 MFMA 32x32 accumulators, lane = row l31, 4 consecutive columns per
-// register quad).  One 32-row block at a time: its 32 x 64 fp32 accumulators go through the wave-private 8 KiB LDS
+// Epilogue of one 128 x 64 wave tile (8 x 4 MFMA 16x16 accumulators, layout at acc_block_to_lds).  One 32-row block at a time: its 32 x 64 fp32 accumulators go through the wave-private 8 KiB LDS
 // image W (16-byte chunk index XORed with row & 7: conflict-free both ways) and come back row-coalesced: lane
 // (crow = lane >> 3, g = lane & 7) holds 8 consecutive columns of row it*8 + crow.  All epilogue math (alpha, bias,
 // activation or act'(U), residual) runs in that layout in fp32 with one rounding; every global access is 16 B per
-// lane = 8 full 128-byte rows per wave instruction.  The accumulators are re-zeroed on the way out.
+// lane = 8 full 128-byte rows per wave instruction.
 // Every global LOAD is hand-issued (buffer_load asm) with counted waits, because the caller may have D LDS-DMA
 // loads of its next tile in flight (issued by issue_dma() right after the epilogue's own loads): a compiler-counted
 // vmcnt would drain them.  VMEM stream (all counts static; Lb: NL loads, Sb: NS stores):
@@ -224,40 +145,16 @@ __device__ __forceinline__ EpiCtx make_epi_ctx(const GemmArgs& p) {
 // written by the next VALU instruction(s).  hipcc pads that hazard for flat/global stores but exempts MUBUF stores
 // that carry an SGPR soffset -- on gfx950 the exemption does not hold (seen as corrupted second dwords in the last
 // lanes of each 16 when a v_pk_fma_f32 reused the data registers right after the builtin's store).
-// EZ_STG_MOD / EZ_STG_SAMEADDR: experiment hooks of tools/build_variants.py (cache-policy bits on the store; all stores
-// of a wave aimed at one 1 KiB region = same instruction stream without the DRAM write traffic).
-// EZ_ABL_NOSTORE / EZ_ABL_NOEPI: timing ablations (results are wrong by construction).
-// Default " nt": C is a write-once stream; the non-temporal hint measured +2 % on the K=768 products and +0.9 % on the
+// " nt": C is a write-once stream; the non-temporal hint measured +2 % on the K=768 products and +0.9 % on the
 // forward step (profiles/README.md, store experiments); sc1 / sc0 sc1 made no difference.
-#ifndef EZ_STG_MOD
-#define EZ_STG_MOD " nt"
-#endif
-#if defined(EZ_ABL_NOSTORE) || defined(EZ_ABL_NOEPI)
-constexpr int kStoresPerBlock = 0;
-#else
 constexpr int kStoresPerBlock = 4;
-#endif
 __device__ __forceinline__ void stg16(const u32x4_t& data, uint32_t voff, const i32x4_t& srd, uint32_t soff) {
-#if defined(EZ_ABL_NOSTORE) || defined(EZ_ABL_NOEPI)
-  asm volatile("" ::"v"(data), "v"(voff), "s"(soff));
-  return;
-#endif
-#if EZ_ROLES
-  if (!ez_store_role()) return;
-#endif
-#ifdef EZ_STG_SAMEADDR
-  voff = (voff & 0x70u) | ((threadIdx.x & 0x1f8u) << 4); soff = 0;
-#endif
-  asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" EZ_STG_MOD "\n\ts_nop 1" ::"v"(data), "v"(voff), "s"(srd), "s"(soff) : "memory");
+  asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen nt\n\ts_nop 1" ::"v"(data), "v"(voff), "s"(srd), "s"(soff) : "memory");
 }
 
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
 // 8-byte store; lanes that must not store pass voff = 0xFFFFFFF0 (out of range: dropped by the descriptor)
 __device__ __forceinline__ void stg8(const u32x2_t& data, uint32_t voff, const i32x4_t& srd, uint32_t soff) {
-#if defined(EZ_ABL_NOSTORE) || defined(EZ_ABL_NOEPI)
-  asm volatile("" ::"v"(data), "v"(voff), "s"(soff));
-  return;
-#endif
   asm volatile("buffer_store_dwordx2 %0, %1, %2, %3 offen\n\ts_nop 0" ::"v"(data), "v"(voff), "s"(srd), "s"(soff) : "memory");
 }
 __device__ __forceinline__ void ldg8(u32x2_t& dst, uint32_t voff, const i32x4_t& srd, uint32_t soff) {
@@ -292,24 +189,8 @@ __device__ __forceinline__ void epilogue_issue_block(const EpiCtx& ec, int mw, i
 // HAS_LN: folded LayerNorm -- y = acc * rstd_m + (-mean_m rstd_m) * c1[n] + c2[n]  (see GemmArgs::ln_stats)
 // HAS_PS: also emit the per-row (sum, sum of squares) of this wave's 64 rounded output columns (GemmArgs::rowstat_part)
 // 32-row block I of a wave tile's accumulators -> the wave's LDS image W (row r at W + 256 r, 16-byte chunk index = column / 4
-// XORed with r & 7); the 32x32 layout zeroes them for the next tile, the 16x16 layout's first K-tile starts from a literal zero.  Two accumulator layouts: 4 x 2 MFMA 32x32 tiles (lane = row l31, columns
-// j*32 + q*8 + h*4 .. +3) and 8 x 4 MFMA 16x16 tiles (lane = row l15 of a 16-row block, columns cb*16 + (lane >> 4)*4 .. +3).
-template <int I>
-__device__ __forceinline__ void acc_block_to_lds(f32x16_t (&acc)[4][2], char* W, int eln) {
-  const int eh = eln >> 5, el31 = eln & 31;
-  const uint32_t wr_row = (uint32_t)el31 * 256u, wr_sw = (uint32_t)(el31 & 7);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const uint32_t ch = (uint32_t)(j * 8 + q * 2 + eh) ^ wr_sw;
-      *reinterpret_cast<float4*>(W + wr_row + (ch << 4)) =
-          make_float4(acc[I][j][q * 4], acc[I][j][q * 4 + 1], acc[I][j][q * 4 + 2], acc[I][j][q * 4 + 3]);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[I][j][r] = 0.f;
-  }
-}
+// XORed with r & 7).  Layout: 8 x 4 MFMA 16x16 tiles (lane = row l15 of a 16-row block, columns cb*16 + (lane >> 4)*4 .. +3); they
+// are not zeroed here, the next tile's first K-tile starts from a literal zero.
 template <int I>
 __device__ __forceinline__ void acc_block_to_lds(Acc16& acc, char* W, int eln) {
   // row 16 u + l15, chunk (4 cb + q4) ^ (row & 7): row & 7 = l15 & 7 for both u, and 4 cb / q4 occupy disjoint bits, so the byte
@@ -326,43 +207,18 @@ __device__ __forceinline__ void acc_block_to_lds(Acc16& acc, char* W, int eln) {
     }
   }
 }
-__device__ __forceinline__ void acc_keep_and_zero(f32x16_t (&acc)[4][2]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      asm volatile("" ::"v"(acc[i][j]));       // keep the MFMAs alive
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    }
-}
-__device__ __forceinline__ void acc_keep_and_zero(Acc16& acc) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      asm volatile("" ::"v"(acc.t[i][j]));
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc.t[i][j][r] = 0.f;
-    }
-}
 
 // ACT >= 0: the activation is this compile-time constant (the `act` argument is ignored and every test on it folds away: straight-line
 // code, no phi copies of the eight outputs per row); ACT < 0: `act` is read at run time.
 // ISSUE0: request block 0's loads here, first thing (same queue order), instead of one K-tile earlier by the caller -- for the two
 // instantiations whose registers do not hold 16 more values across the last K-tile (R + row-stat partials, U + erf-GELU').
 template <bool FAST, bool HAS_R, bool HAS_U, bool HAS_C2, int D, bool HAS_LN = false, bool HAS_PS = false, int ACT = -1, bool ISSUE0 = false,
-          typename ACC, typename IssueDma>
-__device__ __forceinline__ void epilogue_rows(const EpiCtx& ec, ACC& acc, int mw, int nw, char* W, int act_rt,
+          typename IssueDma>
+__device__ __forceinline__ void epilogue_rows(const EpiCtx& ec, Acc16& acc, int mw, int nw, char* W, int act_rt,
                                               EpiLoads& ld, IssueDma&& issue_dma) {
   const int act = ACT >= 0 ? ACT : act_rt;
   constexpr int NL = 4 * ((HAS_R ? 1 : 0) + (HAS_U ? 1 : 0) + (HAS_LN ? 1 : 0));   // loads per 32-row block
   constexpr int NS = kStoresPerBlock * (1 + (HAS_C2 ? 1 : 0) + (HAS_PS ? 1 : 0));   // stores per 32-row block
-#ifdef EZ_ABL_NOEPI
-  issue_dma();
-  acc_keep_and_zero(acc);
-  return;
-#endif
   const int eln = lane_id_now();
   const int crow = eln >> 3, g = eln & 7;
   const uint32_t lane_c = (uint32_t)crow * ec.ldc_b + (uint32_t)g * 16u;
@@ -403,22 +259,13 @@ __device__ __forceinline__ void epilogue_rows(const EpiCtx& ec, ACC& acc, int mw
     }
     // wait for this block's loads (block 0: also the bias)
     if constexpr (i == 0) {
-#if EZ_ROLES
-      wait_role<D, 0, 2 * NL, false>();
-      wait_vm2<63>(bq[0], bq[1]);
-#else
       wait_vm2<2 * NL + D>(bq[0], bq[1]);
-#endif
       bv[0] = __uint_as_float(bq[0].x); bv[1] = __uint_as_float(bq[0].y);
       bv[2] = __uint_as_float(bq[0].z); bv[3] = __uint_as_float(bq[0].w);
       bv[4] = __uint_as_float(bq[1].x); bv[5] = __uint_as_float(bq[1].y);
       bv[6] = __uint_as_float(bq[1].z); bv[7] = __uint_as_float(bq[1].w);
       if constexpr (HAS_LN) {     // (bias is null here: bv = 0 + c2)
-#if EZ_ROLES
-        wait_vm4<63>(c1q[0], c1q[1], c2q[0], c2q[1]);
-#else
         wait_vm4<2 * NL + D>(c1q[0], c1q[1], c2q[0], c2q[1]);
-#endif
         c1v[0] = __uint_as_float(c1q[0].x); c1v[1] = __uint_as_float(c1q[0].y);
         c1v[2] = __uint_as_float(c1q[0].z); c1v[3] = __uint_as_float(c1q[0].w);
         c1v[4] = __uint_as_float(c1q[1].x); c1v[5] = __uint_as_float(c1q[1].y);
@@ -431,15 +278,7 @@ __device__ __forceinline__ void epilogue_rows(const EpiCtx& ec, ACC& acc, int mw
     }
     if constexpr (NL > 0) {
       // newer than block i's loads:  0: (bias) L1 L2 D   1: L2 D S0 L3   2: D S0 L3 S1   3: S1 S2
-#if EZ_ROLES
-      if constexpr (i == 0) wait_role<D, 0, 2 * NL, false>();
-      else if constexpr (i == 1) wait_role<D, NS, 2 * NL, false>();
-      else if constexpr (i == 2) wait_role<D, 2 * NS, NL, false>();
-      else wait_role<0, 2 * NS, 0, false>();
-      constexpr int cnt = 63;
-#else
       constexpr int cnt = (i == 0) ? 2 * NL + D : (i == 1) ? 2 * NL + D + NS : (i == 2) ? NL + D + 2 * NS : 2 * NS;
-#endif
       if constexpr (HAS_R) wait_vm4<cnt>(ld.r[b][0], ld.r[b][1], ld.r[b][2], ld.r[b][3]);
       if constexpr (HAS_U) wait_vm4<cnt>(ld.u[b][0], ld.u[b][1], ld.u[b][2], ld.u[b][3]);
       if constexpr (HAS_LN) wait_vm4s<cnt>(ld.s[b][0], ld.s[b][1], ld.s[b][2], ld.s[b][3]);

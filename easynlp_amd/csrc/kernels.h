@@ -95,9 +95,9 @@ int gemm_nt(GemmArgs p, int dtype, hipStream_t stream);
 bool gemm_nt_uses_8p(const GemmArgs& p, int dtype);
 bool gemm_nt_8p_eligible(const GemmArgs& p, int dtype);
 int gemm_nt_8p(const GemmArgs& p, hipStream_t stream);
-void set_gemm_variant(int v);   // debugging / sweeps: -1 heuristic, 0 = 128x128 tile, 1 = 256x256 tile
-void set_gemm_raster(int gm);   // tile order of the persistent 8-phase kernel (GemmArgs::raster_gm); -1: built-in default
-void set_gemm_dephase(int v);   // staggered first tiles of the persistent 8-phase kernel (gemm8p.hip); 0 off, -1 built-in default
+int set_gemm_variant(int v);    // debugging / sweeps: -1 heuristic, 0 = 128x128 tile, 1 = 256x256 tile, 2 = 8-phase, 3 = 64x64
+int set_gemm_raster(int gm);    // tile order of the persistent 8-phase kernel (GemmArgs::raster_gm); -1: built-in default
+void set_gemm8p_tile_per_workgroup(bool on);   // 8-phase kernel launched with one workgroup per tile (no persistent loop)
 
 // C[N,K] (+)= A[M,N]^T . B[M,K]   (weight gradients; contraction over rows)
 struct GemmTNArgs {

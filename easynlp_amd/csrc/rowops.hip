@@ -274,10 +274,9 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* x, int64_t xs, con
       }
     }
   };
-#ifndef EZ_LNBWD_UNPACKED
   // bf16 rows stay PACKED while in flight (2 VGPRs per 4 elements instead of 4), so four rows per wave fit where two
-  // unpacked ones did -- twice the bytes in flight at the same occupancy.  Same per-row arithmetic in the same order:
-  // results are bit-identical to the unpacked path (-DEZ_LNBWD_UNPACKED keeps it for A/B).  Measured (round 2, 201728
+  // unpacked ones (the f32 path below) did -- twice the bytes in flight at the same occupancy.  Same per-row arithmetic in the
+  // same order: results are bit-identical to running bf16 through the unpacked path.  Measured (round 2, 201728
   // x 768 bf16): 302.6 -> 193.2 us per call, 3.07 -> 4.81 TB/s.
   if constexpr (sizeof(T) == 2) {
     constexpr int R = 4;
@@ -314,7 +313,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* x, int64_t xs, con
       }
     }
   } else
-#endif
   for (int row = gw; row < rows; row += 2 * nwaves) {
     float xa[NC][4], da[NC][4], ra[NC][4], xb[NC][4], dbb[NC][4], rb[NC][4];
     float ma, sa, mb, sb;

@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# EZCLIP_LIB: load another build of the same library (experiment variants of tools/build_variants.py); unset = the in-tree one
+# EZCLIP_LIB: load another build of the same library, e.g. the parent commit's; unset = the in-tree one
 LIB_PATH = os.environ.get("EZCLIP_LIB") or os.path.join(_HERE, "csrc", "libezclip_hip.so")
 
 DTYPE_F32 = 0

@@ -413,19 +413,20 @@ int ezclip_recall_ranks_fused(const float* text_rows_dev, const float* image_dev
 #define EZCLIP_PROF_GEMM 0
 #define EZCLIP_PROF_ATTN 1
 #define EZCLIP_PROF_ROWOP 2
-/* Tuning / A-B switches for sweeps and tests.  key 0: GEMM kernel (-1 heuristic, 0 128x128, 1 256x256 two-phase,
- * 2 8-phase);  key 1: attention kernels (-1 heuristic, 0 general two-pass kernels only);
+/* Tuning / A-B switches for sweeps and tests (keys 0, 6 and 12 refuse values outside their list: EZCLIP_ERR_INVALID).  key 0: GEMM kernel
+ * (-1 heuristic, 0 128x128, 1 256x256 two-phase, 2 8-phase, 3 64x64);  key 1: attention kernels (-1 heuristic, 0 general two-pass kernels only);
  * key 2: LayerNorm folding on the bf16 inference path (0 off, 1 folded + statistics from the producing GEMM, 2 folded +
  * separate statistics pass);  key 3: last-block CLS-only evaluation on the inference path (1 on, 0 off);  key 4: the same on the training path;  key 5: resampling window
  * tables of ezclip_preprocess_images built on the device (1, default) or on the host (0);  key 6: tile order of the persistent
- * GEMM (0 column-fastest, g > 0 super-rows of g row tiles walked column by column, -1 the built-in default);  key 7: BERT
+ * GEMM (0 column-fastest, 1..99: super-rows of g row tiles walked column by column, 101..199: super-columns of g - 100 tile columns,
+ * -1 the built-in default);  key 7: BERT
  * query / key / value projections as one N = 3 * hidden product on the bf16 path (1, default) or three products (0);
  * key 8: the CLS-only last ViT block projects its queries for the CLS rows only (1, default);  key 9: short attention forward:
  * bit 0 short last tile, bit 1 row sums on the matrix pipe (3, default);  key 10: ModifiedResNet tower: bound of one activation
  * buffer in MiB (256; tests lower it to walk a small batch in chunks);  key 11: fused attention backward for sequences up to
  * 256 tokens: 1 (default) the score-tile-once kernel (round 4) up to 128 tokens -- where it measures faster -- and the two-pass
  * kernel of rounds 2-3 beyond, 2 the score-tile-once kernel wherever it is eligible (<= 256 tokens), 0 the two-pass kernel only;
- * key 12: de-phasing of the persistent GEMM's workgroups (staggered first tiles: steps + 100 * period code; 0 off, -1 built-in default). */
+ * key 12: formerly de-phasing of the persistent GEMM's workgroups, now removed: 0 and -1 (off) are accepted and do nothing. */
 int ezclip_debug_set(int key, int value);
 int ezclip_profile_begin(void);
 int ezclip_profile_end(int kernel_class, double* total_ms, double* total_work, int* launches);

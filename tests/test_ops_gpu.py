@@ -534,8 +534,14 @@ def test_attention_bwd_projection_bias_gradients(B_, Lq, H, dtype, masked):
 @pytest.mark.parametrize("M,N,K", [(256, 256, 64), (1000, 768, 768), (513, 512, 128), (2049, 256, 3072), (300, 100, 64)])
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_gemm_nt_tile_variants(M, N, K, dtype, variant):
-    """Both tile shapes (128x128 / 256x256) on ragged M/N, with the full epilogue."""
+    """Both tile shapes (128x128 / 256x256) on ragged M/N, with the full epilogue.  The GEMM debug switches refuse values
+    that select nothing (EZCLIP_ERR_INVALID = 1, nothing stored) and accept the off / default ones."""
     lib = L.load()
+    for key, value in ((0, 4), (0, 24), (6, 100), (6, 200), (6, 10106), (6, -2), (12, 1), (12, 10003)):
+        assert lib.ezclip_debug_set(key, value) == 1, (key, value)
+        assert str(value) in L.last_error()
+    for key, value in ((0, -1), (6, 0), (6, 4), (6, 106), (6, -1), (12, 0), (12, -1)):
+        L.check(lib.ezclip_debug_set(key, value))
     g = torch.Generator().manual_seed(M + N + K + variant)
     a = torch.randn(M, K, generator=g) * 0.5
     b = torch.randn(N, K, generator=g) * 0.2

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """One number per process: the fused two-pass attention backward (with the q / k / v bias gradients, as the towers call it) on the ViT-B/16
-shape, for A/B runs across variant builds (EZCLIP_LIB=tools/bin/var_<name>/libezclip_hip.so) -- ms per launch + a checksum of dq | dk | dv."""
+shape, for A/B runs across builds of the library (EZCLIP_LIB=<another build, e.g. the parent commit's>) -- ms per launch + a checksum of
+dq | dk | dv."""
 import os
 import sys
 import zlib

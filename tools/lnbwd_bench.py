@@ -1,10 +1,9 @@
 #!/usr/bin/env python
 """LayerNorm-backward micro-benchmark (ViT shape of the training workload): time + effective bandwidth.
 
-A/B against the packed-staging experiment (rowops.hip, -DEZ_LNBWD_PACKED: four bf16 rows in flight per wave):
-    python tools/build_variants.py lnpacked@rowops.hip:-DEZ_LNBWD_PACKED
-    python tools/lnbwd_bench.py;  EZCLIP_LIB=tools/bin/var_lnpacked/libezclip_hip.so python tools/lnbwd_bench.py
-(the results must be bit-identical: run tests/test_ops_gpu.py -k layernorm_bwd with the same EZCLIP_LIB)."""
+A/B against another build of the library (EZCLIP_LIB, e.g. the parent commit's):
+    python tools/lnbwd_bench.py;  EZCLIP_LIB=/path/to/other/libezclip_hip.so python tools/lnbwd_bench.py
+(a change to the kernel that should not change its results: run tests/test_ops_gpu.py -k layernorm_bwd with the same EZCLIP_LIB)."""
 import os
 import sys
 import time
